@@ -273,15 +273,24 @@ def test_dashboard_api():
 
 
 def test_partition_cache_spill_bookkeeping():
+    from daft_amd import execution_config_ctx
+    from daft_amd.context import PartitionCache
     ctx = get_context()
-    cache = ctx.cache
-    df1 = daft.from_pydict({"a": list(range(1000))}).collect()
-    df2 = daft.from_pydict({"b": list(range(1000))}).collect()
-    assert cache.total_bytes() > 0
-    # nothing on a cuda device here: spill_lru reports nothing to free
-    assert cache.spill_lru("cuda:0") == 0
-    # host residents are the spill TARGET, never a spill source
-    assert cache.spill_lru("cpu") == 0
+    # a cache of its own, filled by host execution: the context's cache
+    # holds whatever earlier tests left, device-resident partitions included
+    saved, ctx.cache = ctx.cache, PartitionCache()
+    try:
+        cache = ctx.cache
+        with execution_config_ctx(enable_gpu=False):
+            df1 = daft.from_pydict({"a": list(range(1000))}).collect()
+            df2 = daft.from_pydict({"b": list(range(1000))}).collect()
+        assert cache.total_bytes() > 0
+        # nothing on a cuda device here: spill_lru reports nothing to free
+        assert cache.spill_lru("cuda:0") == 0
+        # host residents are the spill TARGET, never a spill source
+        assert cache.spill_lru("cpu") == 0
+    finally:
+        ctx.cache = saved
 
 
 def test_memory_limit_admission():
@@ -526,12 +535,14 @@ def test_native_extension_plugin(tmp_path):
         check=True, capture_output=True)
     names = daft.load_extension(so)
     assert set(names) >= {"ext_add1", "ext_hypot"}
-    df = daft.from_pydict({"a": [1, 2, None], "x": [3.0, 5.0, 8.0],
-                           "y": [4.0, 12.0, 15.0]})
-    out = df.select(
-        daft.ext_function("ext_add1", col("a")).alias("a1"),
-        daft.ext_function("ext_hypot", col("x"), col("y")).alias("h"),
-    ).to_pydict()
+    # the example plugin's functions are host-only
+    with daft.execution_config_ctx(enable_gpu=False):
+        df = daft.from_pydict({"a": [1, 2, None], "x": [3.0, 5.0, 8.0],
+                               "y": [4.0, 12.0, 15.0]})
+        out = df.select(
+            daft.ext_function("ext_add1", col("a")).alias("a1"),
+            daft.ext_function("ext_hypot", col("x"), col("y")).alias("h"),
+        ).to_pydict()
     assert out["a1"] == [2, 3, None]
     assert out["h"] == [5.0, 13.0, 17.0]
 

@@ -501,9 +501,13 @@ def test_projection_cse_evaluates_shared_subtree_once():
         return orig(self, batch)
     E.BinaryOp.evaluate = spy
     try:
-        df = daft.from_pydict({"a": [1, 2], "b": [10, 20]})
-        out = df.select(((col("a") + col("b")) * 2).alias("x"),
-                        ((col("a") + col("b")) - 1).alias("y")).to_pydict()
+        # host execution: on a device the projection is fused and never
+        # reaches BinaryOp.evaluate, so the spy would count nothing
+        with daft.execution_config_ctx(enable_gpu=False):
+            df = daft.from_pydict({"a": [1, 2], "b": [10, 20]})
+            out = df.select(
+                ((col("a") + col("b")) * 2).alias("x"),
+                ((col("a") + col("b")) - 1).alias("y")).to_pydict()
     finally:
         E.BinaryOp.evaluate = orig
     assert out == {"x": [22, 44], "y": [10, 21]}

@@ -199,13 +199,14 @@ def test_wide_group_and_join_keys_cpu():
     with a clear NotImplementedError (kernels _descs / hash_columns)."""
     a = D("12345678901234567890123456.789")
     vals = [a, D("2.5"), a, D("2.5"), D("-7.1")]
-    df = daft.from_pydict({"d": vals, "x": [1, 2, 3, 4, 5]})
-    out = df.groupby("d").agg(col("x").sum().alias("s")).sort("s") \
-        .to_pydict()
-    assert out["s"] == [4, 5, 6]
-    df2 = daft.from_pydict({"d": [D("2.5"), D("-7.1")], "y": [10, 20]})
-    j = df.join(df2, on="d").sort("x").to_pydict()
-    assert j["x"] == [2, 4, 5] and j["y"] == [10, 10, 20]
+    with daft.execution_config_ctx(enable_gpu=False):
+        df = daft.from_pydict({"d": vals, "x": [1, 2, 3, 4, 5]})
+        out = df.groupby("d").agg(col("x").sum().alias("s")).sort("s") \
+            .to_pydict()
+        assert out["s"] == [4, 5, 6]
+        df2 = daft.from_pydict({"d": [D("2.5"), D("-7.1")], "y": [10, 20]})
+        j = df.join(df2, on="d").sort("x").to_pydict()
+        assert j["x"] == [2, 4, 5] and j["y"] == [10, 10, 20]
 
 
 def test_wide_hash_partition_raises():
