@@ -13,28 +13,24 @@ Tensor pack_descs(const std::vector<int64_t>& tags,
                   const std::vector<OptTensor>& offsets,
                   const std::vector<OptTensor>& validities);
 
-// hashing
+// hashing (kernels.hip)
 Tensor hash_rows(const std::vector<int64_t>& tags,
                  const std::vector<Tensor>& datas,
                  const std::vector<OptTensor>& offsets,
                  const std::vector<OptTensor>& validities, int64_t n,
                  int64_t seed);
 
-// selection
+// selection (kernels.hip)
 Tensor compact_indices(Tensor mask);
 std::vector<Tensor> take_string(Tensor offsets, Tensor bytes, Tensor idx);
 Tensor merge_strings(Tensor mask, Tensor t_off, Tensor t_bytes, Tensor f_off,
                      Tensor f_bytes, Tensor out_off);
 
-// groupby
+// groupby (kernels.hip)
 std::vector<Tensor> groupby(Tensor hashes, const std::vector<int64_t>& tags,
                             const std::vector<Tensor>& datas,
                             const std::vector<OptTensor>& offsets,
                             const std::vector<OptTensor>& validities);
-std::vector<Tensor> grouped_agg(Tensor group_ids, int64_t num_groups,
-                                Tensor values, Tensor valid,
-                                const std::string& op);
-Tensor grouped_count(Tensor group_ids, int64_t num_groups, Tensor valid);
 Tensor dense_first_index(Tensor packed, int64_t rng, int64_t sentinel);
 Tensor count_distinct_pairs(Tensor hashes, const std::vector<int64_t>& tags,
                             const std::vector<Tensor>& datas,
@@ -42,7 +38,23 @@ Tensor count_distinct_pairs(Tensor hashes, const std::vector<int64_t>& tags,
                             const std::vector<OptTensor>& validities,
                             Tensor gids, int64_t num_groups);
 
-// join
+// grouped aggregation (groupagg.hip).  Op codes shared with
+// daft_amd/kernels/__init__.py (AGG_*).
+enum AggOp : int { AGG_SUM = 0, AGG_MIN = 1, AGG_MAX = 2, AGG_COUNT = 3 };
+struct MAggCol {  // one aggregate of grouped_multi_agg, packed as 3 x i64
+  const double* data;
+  const bool* valid;
+  int64_t op;
+};
+std::vector<Tensor> grouped_agg(Tensor group_ids, int64_t num_groups,
+                                Tensor values, Tensor valid, int64_t op);
+Tensor grouped_count(Tensor group_ids, int64_t num_groups, Tensor valid);
+std::vector<Tensor> grouped_multi_agg(Tensor gids, int64_t num_groups,
+                                      std::vector<Tensor> datas,
+                                      std::vector<OptTensor> valids,
+                                      std::vector<int64_t> ops);
+
+// join (kernels.hip)
 std::vector<Tensor> join_build(Tensor hashes);
 std::vector<Tensor> join_probe(
     Tensor table, Tensor next, Tensor probe_hashes, Tensor build_hashes,
@@ -52,23 +64,15 @@ std::vector<Tensor> join_probe(
     const std::vector<OptTensor>& off_r, const std::vector<OptTensor>& val_r,
     int64_t mode);
 
-// sort
+// sort (sort.hip)
 Tensor radix_argsort(Tensor keys);
 Tensor string_chunk_key(Tensor offsets, Tensor bytes, int64_t chunk);
 
-// partition
+// partition (kernels.hip)
 Tensor u64_mod(Tensor hashes, int64_t n_partitions);
 
 // multimodal (multimodal.hip)
 Tensor simhash(Tensor offsets, Tensor bytes, int64_t ngram_size);
-std::vector<Tensor> grouped_multi_agg(Tensor gids, int64_t num_groups,
-                                      std::vector<Tensor> datas,
-                                      std::vector<OptTensor> valids,
-                                      std::vector<int64_t> ops);
-std::vector<Tensor> grouped_multi_agg_big(Tensor gids, int64_t num_groups,
-                                          std::vector<Tensor> datas,
-                                          std::vector<OptTensor> valids,
-                                          std::vector<int64_t> ops);
 Tensor minhash(Tensor offsets, Tensor bytes, int64_t num_hashes,
                int64_t ngram_size, Tensor perm_a, Tensor perm_b);
 Tensor hll_update(Tensor hashes, Tensor gids, Tensor valid,

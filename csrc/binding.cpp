@@ -12,6 +12,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("groupby", &groupby, "hash groupby -> (group_ids, rep_idx)");
   m.def("grouped_agg", &grouped_agg, "per-group sum/min/max + valid counts");
   m.def("grouped_count", &grouped_count, "per-group row counts (LDS staged)");
+  m.def("grouped_multi_agg", &grouped_multi_agg,
+        "one-pass f64 sum/min/max/count of several columns");
   m.def("dense_first_index", &dense_first_index,
         "first-occurrence index per packed dense key");
   m.def("count_distinct_pairs", &count_distinct_pairs,
@@ -23,8 +25,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "big-endian 8-byte chunk keys for string sorting");
   m.def("u64_mod", &u64_mod, "unsigned modulo for hash partitioning");
   m.def("simhash", &simhash);
-  m.def("grouped_multi_agg", &grouped_multi_agg);
-  m.def("grouped_multi_agg_big", &grouped_multi_agg_big);
   m.def("minhash", &minhash, "word-ngram MinHash signatures (wave/row)");
   m.def("hll_update", &hll_update, "HyperLogLog register updates");
   m.def("image_resize", &image_resize, "bilinear uint8 HWC resize");

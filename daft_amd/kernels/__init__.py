@@ -53,6 +53,8 @@ def native_required():
 # tags shared with csrc/row_ops.h
 _TAG_W1, _TAG_W2, _TAG_W4, _TAG_W8, _TAG_STR = 0, 1, 2, 3, 4
 _TAG_F32, _TAG_F64 = 5, 6
+# grouped-aggregation op codes shared with csrc/api.h (enum AggOp)
+AGG_SUM, AGG_MIN, AGG_MAX, AGG_COUNT = 0, 1, 2, 3
 
 
 def _col_desc(s: Series):

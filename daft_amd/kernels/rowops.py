@@ -18,7 +18,8 @@ import torch
 
 from ..schema import DataType, TypeKind
 from ..series import Series
-from . import _descs, _is_gpu, native_required, load_native
+from . import (AGG_COUNT, AGG_MAX, AGG_MIN, AGG_SUM, _descs, _is_gpu,
+               native_required, load_native)
 
 _SIGN64 = -0x8000000000000000  # 1 << 63 as int64
 
@@ -284,16 +285,62 @@ def _dense_range_groupby(keys):
 
 
 _SEG_MIN_GROUPS = 1 << 16   # atomics win below this; clustered-key wins above
+_AGG_OPS = {"sum": AGG_SUM, "min": AGG_MIN, "max": AGG_MAX}
+
+
+def gids_sorted(gids: torch.Tensor) -> bool:
+    if gids.numel() < 2:
+        return True
+    return bool((gids[1:] >= gids[:-1]).all().item())
+
+
+def segment_bounds(gids: torch.Tensor, num_groups: int):
+    """(starts, bounds, lengths) of dense sorted gids: segment k == group k,
+    boundaries from one vectorized searchsorted.  Callers keep all three
+    alive while they reduce, as the code always has: torch.segment_reduce
+    leaves outputs past about 2^24 segments unwritten (see
+    profiles/groupagg_refactor.md), so until that is fixed a result of that
+    size depends on which cached block its output lands in."""
+    starts = torch.searchsorted(gids, torch.arange(
+        num_groups, dtype=gids.dtype, device=gids.device))
+    bounds = torch.cat([starts, torch.tensor(
+        [gids.numel()], dtype=starts.dtype, device=gids.device)])
+    return starts, bounds, torch.diff(bounds)
+
+
+_SEG_REDUCE = {AGG_SUM: ("sum", 0.0), AGG_MIN: ("min", float("inf")),
+               AGG_MAX: ("max", float("-inf"))}
+
+
+def segmented_reduce(gids, num_groups, data, validity, op, lengths=None):
+    """Aggregate f64 `data` per group of dense SORTED gids (orderkey-clustered
+    aggregations, q21/q18) with torch.segment_reduce instead of scattered
+    global atomics.  op is an AGG_* code; AGG_COUNT ignores data.  Returns
+    (out[num_groups] f64, valid_count[num_groups] i64).  `lengths` lets a
+    caller reducing several columns share one segment_bounds()."""
+    if lengths is None:
+        _starts, _bounds, lengths = segment_bounds(gids, num_groups)
+    if validity is None:
+        cnt = lengths.to(torch.int64)
+    else:
+        # f64 partial sums count exactly up to 2^53 rows per group
+        cnt = torch.segment_reduce(validity.to(torch.float64), "sum",
+                                   lengths=lengths).to(torch.int64)
+    if op == AGG_COUNT:
+        return torch.zeros(num_groups, dtype=torch.float64,
+                           device=gids.device), cnt
+    red, ident = _SEG_REDUCE[op]
+    if validity is not None:
+        data = torch.where(validity, data, torch.full_like(data, ident))
+    return torch.segment_reduce(data, red, lengths=lengths,
+                                initial=ident), cnt
 
 
 def _segmented_grouped_agg(gid, num_groups, d, validity, op, dev):
-    """Sorted dense gids (orderkey-clustered aggregations, q21/q18):
-    torch.segment_reduce over searchsorted boundaries instead of scattered
-    global atomics.  Returns (out, cnt) or None when not applicable."""
-    n = gid.numel()
-    if num_groups < _SEG_MIN_GROUPS or n < 2:
-        return None
-    if not bool((gid[1:] >= gid[:-1]).all().item()):
+    """Segmented path of grouped_agg.  Returns (out, cnt) or None when not
+    applicable."""
+    if num_groups < _SEG_MIN_GROUPS or gid.numel() < 2 or \
+            not gids_sorted(gid):
         return None
     int_in = not d.dtype.is_floating_point
     if int_in:
@@ -303,26 +350,7 @@ def _segmented_grouped_agg(gid, num_groups, d, validity, op, dev):
         if d.numel() and int(d.abs().max().item()) >= (1 << 53):
             return None
         d = d.to(torch.float64)
-    starts = torch.searchsorted(gid, torch.arange(
-        num_groups, dtype=gid.dtype, device=dev))
-    bounds = torch.cat([starts, torch.tensor([n], dtype=starts.dtype,
-                                             device=dev)])
-    lengths = torch.diff(bounds)
-    if validity is None:
-        cnt = lengths.to(torch.int64)
-        dd = d
-    else:
-        cnt = torch.segment_reduce(validity.to(torch.float32), "sum",
-                                   lengths=lengths).to(torch.int64)
-        if op == "sum":
-            dd = torch.where(validity, d, torch.zeros_like(d))
-        else:
-            fill = float("inf") if op == "min" else float("-inf")
-            dd = torch.where(validity, d, torch.full_like(d, fill))
-    out = torch.segment_reduce(dd, op, lengths=lengths,
-                               initial=0.0 if op == "sum" else
-                               (float("inf") if op == "min"
-                                else float("-inf")))
+    out, cnt = segmented_reduce(gid, num_groups, d, validity, _AGG_OPS[op])
     if int_in:
         out = out.to(torch.int64)
     return out, cnt
@@ -353,9 +381,7 @@ def grouped_agg(group_ids: torch.Tensor, num_groups: int, values: Series,
     data = values.data
     validity = values.validity
 
-    if _phys_float(values.dtype):
-        wdt = torch.float64
-    elif values.dtype.kind == TypeKind.FLOAT32:
+    if _phys_float(values.dtype) or values.dtype.kind == TypeKind.FLOAT32:
         wdt = torch.float64
     else:
         wdt = torch.int64
@@ -372,11 +398,8 @@ def grouped_agg(group_ids: torch.Tensor, num_groups: int, values: Series,
             return seg
         vmask = validity if validity is not None else \
             torch.empty(0, dtype=torch.bool, device=dev)
-        out, cnt = native_required().grouped_agg(gid, num_groups, d, vmask, op)
-        if validity is None and cnt is not None:
-            # kernel counted every row (no validity): cnt is still exact
-            pass
-        return out, cnt
+        return native_required().grouped_agg(gid, num_groups, d, vmask,
+                                             _AGG_OPS[op])
 
     # CPU fallback via scatter_reduce
     vmask = validity if validity is not None else \

@@ -1,7 +1,8 @@
 """Hash groupby-aggregate execution (ref:
 /root/reference/src/daft-local-execution/src/sinks/grouped_aggregate.rs and
 daft-recordbatch/src/ops/agg.rs).  The hash-table build runs as a HIP kernel
-(csrc/groupby.hip) on GPU; per-group reductions are atomic HIP kernels.
+(csrc/kernels.hip) on GPU; per-group reductions are atomic HIP kernels
+(csrc/groupagg.hip).
 
 Also implements agg-expression decomposition: an agg output expression is an
 arbitrary tree over Agg nodes (e.g. ``sum(a*b) / sum(c) + 1``); we extract the
@@ -16,7 +17,7 @@ import torch
 
 from ..expressions.expressions import (Agg, AggKind, Alias, ColumnRef,
                                        ExprNode)
-from ..kernels import rowops
+from ..kernels import AGG_COUNT, AGG_MAX, AGG_MIN, AGG_SUM, rowops
 from ..recordbatch import RecordBatch
 from ..schema import DataType, Field, Schema, TypeKind
 from ..series import Series, full_null
@@ -367,52 +368,14 @@ _MULTI_AGG_KINDS = {AggKind.SUM, AggKind.MIN, AggKind.MAX, AggKind.MEAN,
                     AggKind.COUNT, AggKind.COUNT_ALL}
 
 
-def _gids_sorted(gids: torch.Tensor) -> bool:
-    if gids.numel() < 2:
-        return True
-    return bool((gids[1:] >= gids[:-1]).all().item())
-
-
 def _segmented_multi_agg(gids, num_groups, datas, valids, ops, n, dev):
-    """Sorted-gids multi-aggregate via torch.segment_reduce.  gids are
-    dense AND sorted, so segment k == group k and boundaries come from
-    one vectorized searchsorted.  Output layout matches
-    grouped_multi_agg_big: (flat out[n_aggs*G] f64, cnt[n_aggs*G] i64)."""
-    G = num_groups
-    starts = torch.searchsorted(gids, torch.arange(
-        G, dtype=gids.dtype, device=dev))
-    bounds = torch.cat([starts, torch.tensor([n], dtype=starts.dtype,
-                                             device=dev)])
-    lengths = torch.diff(bounds)
-    outs = []
-    cnts = []
-    for d, v, op in zip(datas, valids, ops):
-        if v is None:
-            cnt = lengths.to(torch.int64)
-        else:
-            cnt = torch.segment_reduce(v.to(torch.float64), "sum",
-                                       lengths=lengths).to(torch.int64)
-        if op == 3:       # count only
-            outs.append(torch.zeros(G, dtype=torch.float64, device=dev))
-            cnts.append(cnt)
-            continue
-        if op == 0:       # sum
-            dd = d if v is None else torch.where(
-                v, d, torch.zeros_like(d))
-            red = "sum"
-        elif op == 1:     # min
-            dd = d if v is None else torch.where(
-                v, d, torch.full_like(d, float("inf")))
-            red = "min"
-        else:             # max
-            dd = d if v is None else torch.where(
-                v, d, torch.full_like(d, float("-inf")))
-            red = "max"
-        outs.append(torch.segment_reduce(dd, red, lengths=lengths,
-                                         initial=0 if red == "sum" else
-                                         (float("inf") if red == "min"
-                                          else float("-inf"))))
-        cnts.append(cnt)
+    """Sorted-gids multi-aggregate: rowops.segmented_reduce per column over
+    shared segment lengths.  Output layout matches the native
+    grouped_multi_agg: (flat out[n_aggs*G] f64, cnt[n_aggs*G] i64)."""
+    _starts, _bounds, lengths = rowops.segment_bounds(gids, num_groups)
+    outs, cnts = zip(*(rowops.segmented_reduce(gids, num_groups, d, v, op,
+                                               lengths)
+                       for d, v, op in zip(datas, valids, ops)))
     return torch.cat(outs), torch.cat(cnts)
 
 
@@ -457,7 +420,7 @@ def _multi_agg(batch, gids, num_groups, named_aggs, mask):
                                            a.child is None):
             datas.append(torch.empty(0, dtype=torch.float64, device=dev))
             valids.append(mask)
-            ops.append(3)
+            ops.append(AGG_COUNT)
             meta.append((cname, a, None))
             continue
         key = repr(a.child)
@@ -476,22 +439,22 @@ def _multi_agg(batch, gids, num_groups, named_aggs, mask):
         if a.kind == AggKind.COUNT:
             datas.append(torch.empty(0, dtype=torch.float64, device=dev))
             valids.append(v)
-            ops.append(3)
+            ops.append(AGG_COUNT)
         else:
             datas.append(d.contiguous())
             valids.append(v.contiguous() if v is not None else None)
-            ops.append({AggKind.SUM: 0, AggKind.MIN: 1, AggKind.MAX: 2,
-                        AggKind.MEAN: 0}[a.kind])
+            ops.append({AggKind.SUM: AGG_SUM, AggKind.MIN: AGG_MIN,
+                        AggKind.MAX: AGG_MAX, AggKind.MEAN: AGG_SUM}[a.kind])
         meta.append((cname, a, values))
-    if big and num_groups > 1 and _gids_sorted(gids):
+    if big and num_groups > 1 and rowops.gids_sorted(gids):
         # clustered keys (lineitem is orderkey-ordered: the q21/q18
         # per-order aggregations): segmented reduction instead of 1.5B
         # scattered global atomics
         out, cnt = _segmented_multi_agg(gids, num_groups, datas, valids,
                                         ops, n, dev)
     else:
-        fn = nat.grouped_multi_agg_big if big else nat.grouped_multi_agg
-        out, cnt = fn(gids, num_groups, datas, valids, ops)
+        out, cnt = nat.grouped_multi_agg(gids, num_groups, datas, valids,
+                                         ops)
     out = out.view(len(named_aggs), num_groups)
     cnt = cnt.view(len(named_aggs), num_groups)
     cols = []

@@ -18,6 +18,7 @@ setup(
             sources=[
                 "csrc/binding.cpp",
                 "csrc/kernels.hip",
+                "csrc/groupagg.hip",
                 "csrc/sort.hip",
                 "csrc/strings.hip",
                 "csrc/multimodal.hip",

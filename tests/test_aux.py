@@ -1071,6 +1071,47 @@ def test_segmented_multi_agg_matches_scatter():
     assert torch.equal(cnt[0], ref_cv)
 
 
+def test_segmented_reduce_matches_numpy():
+    """The shared segmented helper against a numpy scatter reference at
+    far more groups than rows, and its valid-row count past 2^24 rows in
+    one group (exact in float64, not in float32)."""
+    import numpy as np
+    import torch
+    from daft_amd.kernels import AGG_COUNT, AGG_MAX, AGG_MIN, AGG_SUM
+    from daft_amd.kernels.rowops import segment_bounds, segmented_reduce
+    rng = np.random.default_rng(9)
+    n, G = 5000, 70_000
+    g = np.sort(rng.integers(0, G, n))
+    d = rng.integers(-(1 << 20), 1 << 20, n) / 1024.0   # exact sums
+    v = rng.random(n) > 0.2
+    tg, td, tv = torch.from_numpy(g), torch.from_numpy(d), torch.from_numpy(v)
+    for valid in (None, v):
+        keep = np.ones(n, bool) if valid is None else valid
+        want_cnt = np.zeros(G, np.int64)
+        np.add.at(want_cnt, g[keep], 1)
+        ref = {AGG_SUM: (np.add, 0.0), AGG_MIN: (np.minimum, np.inf),
+               AGG_MAX: (np.maximum, -np.inf)}
+        for op, (ufunc, ident) in ref.items():
+            want = np.full(G, ident)
+            ufunc.at(want, g[keep], d[keep])
+            out, cnt = segmented_reduce(tg, G, td,
+                                        None if valid is None else tv, op)
+            assert np.array_equal(out.numpy(), want), op
+            assert cnt.dtype == torch.int64
+            assert np.array_equal(cnt.numpy(), want_cnt), op
+        out, cnt = segmented_reduce(tg, G, None,
+                                    None if valid is None else tv, AGG_COUNT)
+        assert np.array_equal(cnt.numpy(), want_cnt) and not out.any()
+    assert np.array_equal(segment_bounds(tg, G)[2].numpy(),
+                          np.bincount(g, minlength=G))
+    # one group of 2^24 + 3 valid rows, fed as a lengths tensor
+    big = (1 << 24) + 3
+    _, cnt = segmented_reduce(torch.zeros(big, dtype=torch.int64), 1, None,
+                              torch.ones(big, dtype=torch.bool), AGG_COUNT,
+                              lengths=torch.tensor([big]))
+    assert cnt.tolist() == [big]
+
+
 def test_round2_edge_cases():
     """Empty inputs through the round-2 surfaces: new optimizer rules,
     external sort, jq, Map, is_in table path, scan tasks, framed windows."""

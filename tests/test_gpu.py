@@ -116,6 +116,56 @@ def test_join_string_keys_gpu():
     assert g == {"k": ["bb", "bb", "ccc"], "v": [1, 1, 2]}
 
 
+def test_join_null_and_duplicate_keys_gpu():
+    """All four probe modes with ~10 % null keys on both sides and build
+    keys repeated up to 5 times, against the CPU join."""
+    import random
+    random.seed(11)
+    rk = []
+    for k in range(0, 1600, 2):
+        rk += [k] * random.randint(1, 5)
+    random.shuffle(rk)
+    rk = [None if random.random() < 0.1 else k for k in rk]
+    rv = list(range(len(rk)))
+    nl = 4000
+    lk = [None if random.random() < 0.1 else random.randrange(1600)
+          for _ in range(nl)]
+    li = list(range(nl))
+
+    def rows(dev, how):
+        out = daft.from_pydict({"k": lk, "i": li}, device=dev).join(
+            daft.from_pydict({"k": rk, "v": rv}, device=dev),
+            on="k", how=how).to_pydict()
+        names = sorted(out)
+        return names, sorted(
+            zip(*(out[c] for c in names)),
+            key=lambda r: tuple((x is None, x or 0) for x in r))
+
+    for how in ("inner", "left", "semi", "anti"):
+        got, want = rows("cuda:0", how), rows("cpu", how)
+        assert got == want, how
+        assert want[1], how          # every mode yields rows
+
+
+def test_if_else_strings_gpu():
+    """if_else over two string columns (the byte-merge kernel) with nulls
+    and empty strings, against the CPU path."""
+    n = 3000
+    data = {
+        "c": [bool((i * 7) % 3) for i in range(n)],
+        "a": [None if i % 11 == 0 else "a" * (i % 7) + str(i)
+              for i in range(n)],
+        "b": [None if i % 13 == 0 else "" if i % 5 == 0 else f"b{i}" * 2
+              for i in range(n)],
+    }
+    q = lambda df: df.select(
+        col("c").if_else(col("a"), col("b")).alias("r")).to_pydict()
+    got = q(daft.from_pydict(data, device="cuda:0"))
+    want = q(daft.from_pydict(data, device="cpu"))
+    assert got == want
+    assert want["r"][:4] == [None, "a1", "aa2", "b3b3"]
+
+
 def test_radix_argsort_vs_torch():
     torch.manual_seed(6)
     for n in (1, 63, 64, 1000, 1_000_000):
