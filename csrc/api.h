@@ -115,7 +115,7 @@ Tensor str_like(Tensor offsets, Tensor bytes, Tensor needles, Tensor lens,
                 bool anchored_prefix, bool anchored_suffix);
 Tensor str_case(Tensor offsets, Tensor bytes, int64_t mode);
 std::vector<Tensor> str_substr(Tensor offsets, Tensor bytes, int64_t start,
-                               int64_t length);
+                               int64_t length, bool by_char);
 std::vector<Tensor> str_concat(const std::vector<Tensor>& offsets,
                                const std::vector<Tensor>& bytes);
 Tensor str_char_length(Tensor offsets, Tensor bytes);

@@ -31,7 +31,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("str_find", &str_find, "substring find/prefix/suffix");
   m.def("str_like", &str_like, "ordered multi-substring LIKE");
   m.def("str_case", &str_case, "ASCII upper/lower");
-  m.def("str_substr", &str_substr, "byte substring");
+  m.def("str_substr", &str_substr, "substring by code points or bytes");
   m.def("str_concat", &str_concat, "row-wise string concat");
   m.def("str_char_length", &str_char_length, "UTF-8 character length");
   m.def("string_compare", &string_compare, "lexicographic compare");

@@ -167,8 +167,52 @@ Tensor str_case(Tensor offsets, Tensor bytes, int64_t mode) {
   return out;
 }
 
-__global__ void substr_copy_kernel(const int64_t* src_off,
-                                   const uint8_t* src_bytes, int64_t start,
+// The one UTF-8 walk: byte offset in s[0, len) of code point `k`, or `len`
+// when the row has fewer; *seen = code points before that offset.  A code
+// point starts at every byte that is not a 10xxxxxx continuation byte.
+DEV_INLINE int64_t utf8_offset_of_char(const uint8_t* s, int64_t len,
+                                       int64_t k, int64_t* seen) {
+  int64_t cnt = 0, j = 0;
+  for (; j < len; ++j) {
+    if ((s[j] & 0xC0) != 0x80) {
+      if (cnt == k) break;
+      ++cnt;
+    }
+  }
+  *seen = cnt;
+  return j;
+}
+
+// Per row: where the substring starts in src_bytes and how many bytes it
+// has.  start >= 0; length < 0 means to the end of the row.  by_char counts
+// code points (STRING), otherwise bytes (BINARY).
+__global__ void substr_bounds_kernel(const int64_t* offs,
+                                     const uint8_t* bytes, int64_t n,
+                                     int64_t start, int64_t length,
+                                     bool by_char, int64_t* src_start,
+                                     int64_t* out_len) {
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    int64_t a = offs[i], len = offs[i + 1] - a;
+    int64_t bs, bl;
+    if (by_char) {
+      int64_t seen;
+      bs = utf8_offset_of_char(bytes + a, len, start, &seen);
+      bl = length < 0 ? len - bs
+                      : utf8_offset_of_char(bytes + a + bs, len - bs, length,
+                                            &seen);
+    } else {
+      bs = min(start, len);
+      bl = length < 0 ? len - bs : min(length, len - bs);
+    }
+    src_start[i] = a + bs;
+    out_len[i] = bl;
+  }
+}
+
+__global__ void substr_copy_kernel(const int64_t* src_start,
+                                   const uint8_t* src_bytes,
                                    const int64_t* out_off, int64_t n,
                                    int64_t total, uint8_t* out) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -181,27 +225,37 @@ __global__ void substr_copy_kernel(const int64_t* src_off,
       if (out_off[mid + 1] <= j) lo = mid + 1; else hi = mid;
     }
     int64_t within = j - out_off[lo];
-    out[j] = src_bytes[src_off[lo] + start + within];
+    out[j] = src_bytes[src_start[lo] + within];
   }
 }
 
 std::vector<Tensor> str_substr(Tensor offsets, Tensor bytes, int64_t start,
-                               int64_t length) {
+                               int64_t length, bool by_char) {
+  TORCH_CHECK(start >= 0, "str_substr: start must be >= 0, got ", start);
   auto dev = offsets.device();
   int64_t n = offsets.numel() - 1;
-  auto lens = offsets.slice(0, 1) - offsets.slice(0, 0, n);
-  auto new_lens = (lens - start).clamp(0);
-  if (length >= 0) new_lens = new_lens.clamp(0, length);
-  auto out_off = torch::zeros({n + 1}, torch::dtype(torch::kInt64).device(dev));
-  if (n > 0) out_off.slice(0, 1).copy_(torch::cumsum(new_lens, 0));
+  auto opts64 = torch::dtype(torch::kInt64).device(dev);
+  auto src_start = torch::empty({n}, opts64);
+  auto new_lens = torch::empty({n}, opts64);
+  auto out_off = torch::zeros({n + 1}, opts64);
+  int block = 256;
+  if (n > 0) {
+    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
+    hipLaunchKernelGGL(substr_bounds_kernel, dim3(grid_1d(n, block)),
+                       dim3(block), 0, str_stream(),
+                       offsets.data_ptr<int64_t>(), bp, n, start, length,
+                       by_char, src_start.data_ptr<int64_t>(),
+                       new_lens.data_ptr<int64_t>());
+    out_off.slice(0, 1).copy_(torch::cumsum(new_lens, 0));
+  }
   int64_t total = n > 0 ? out_off[n].item<int64_t>() : 0;
   auto out = torch::empty({total}, torch::dtype(torch::kUInt8).device(dev));
   if (total > 0) {
-    int block = 256;
     hipLaunchKernelGGL(substr_copy_kernel, dim3(grid_1d(total, block)),
                        dim3(block), 0, str_stream(),
-                       offsets.data_ptr<int64_t>(), bytes.data_ptr<uint8_t>(),
-                       start, out_off.data_ptr<int64_t>(), n, total,
+                       src_start.data_ptr<int64_t>(),
+                       bytes.data_ptr<uint8_t>(),
+                       out_off.data_ptr<int64_t>(), n, total,
                        out.data_ptr<uint8_t>());
   }
   return {out_off, out};
@@ -264,9 +318,8 @@ __global__ void char_length_kernel(const int64_t* offs, const uint8_t* bytes,
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
     int64_t a = offs[i], b = offs[i + 1];
-    int64_t cnt = 0;
-    for (int64_t j = a; j < b; ++j)
-      cnt += (bytes[j] & 0xC0) != 0x80;  // count non-continuation bytes
+    int64_t cnt;
+    utf8_offset_of_char(bytes + a, b - a, INT64_MAX, &cnt);
     out[i] = cnt;
   }
 }

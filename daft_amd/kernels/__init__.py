@@ -882,7 +882,9 @@ def if_else(cond: Series, t: Series, f: Series) -> Series:
         if bool(validity.all().item()):
             validity = None
         return Series(t.name, out_dt, data=out, validity=validity)
-    # variable width: select via take
+    # variable width: select via take (the merge works on offsets + bytes,
+    # so dictionary-encoded sides are materialized first)
+    t, f = t.dict_decode(), f.dict_decode()
     idx = torch.arange(n, dtype=torch.int64, device=t.device)
     t_idx = torch.where(m, idx, torch.full_like(idx, -1))
     f_idx = torch.where(m, torch.full_like(idx, -1), idx)

@@ -766,6 +766,10 @@ def _max_strlen(s: Series) -> int:
     return int(lens.max().item())
 
 
+def _has_nul_byte(s: Series) -> bool:
+    return s.data.numel() > 0 and bool((s.data == 0).any().item())
+
+
 def _stable_sort_perm_by(keys: torch.Tensor) -> torch.Tensor:
     """Stable ascending argsort of u64-encoded keys (int64 bit pattern,
     compared as unsigned)."""
@@ -840,6 +844,17 @@ def _try_composed_argsort(keys, descending, nulls_first):
     return _stable_sort_perm_by(packed)
 
 
+def _value_pass(s: Series, k: torch.Tensor, desc: bool,
+                perm: torch.Tensor) -> torch.Tensor:
+    """One stable LSD pass over `perm` by the u64-ordered key `k` of `s`."""
+    if desc:
+        k = ~k
+    if s.validity is not None:
+        # whatever lies under a null row must not order the nulls
+        k = torch.where(s.validity, k, torch.zeros_like(k))
+    return perm[_stable_sort_perm_by(k[perm])]
+
+
 def argsort_multi(keys: Sequence[Series], descending: Sequence[bool],
                   nulls_first: Sequence[bool]) -> torch.Tensor:
     """Stable lexicographic argsort over multiple key columns."""
@@ -879,25 +894,19 @@ def argsort_multi(keys: Sequence[Series], descending: Sequence[bool],
                                device=s.device)
             rank[vperm] = torch.arange(len(vocab), dtype=torch.int64,
                                        device=s.device)
-            k = rank[s.data.to(torch.int64)]
-            if desc:
-                k = ~k
-            kg = k[perm]
-            perm = perm[_stable_sort_perm_by(kg)]
+            perm = _value_pass(s, rank[s.data.to(torch.int64)], desc, perm)
         elif s.dtype.kind in (TypeKind.STRING, TypeKind.BINARY):
+            if _has_nul_byte(s):
+                # chunk keys are zero padded, so "a" and "a\0" tie on every
+                # chunk: a least-significant pass on byte length puts the
+                # shorter one first
+                perm = _value_pass(s, s.offsets[1:] - s.offsets[:-1], desc,
+                                   perm)
             nchunks = max(1, (_max_strlen(s) + 7) // 8)
             for c in range(nchunks - 1, -1, -1):
-                k = _string_chunk_key(s, c)
-                if desc:
-                    k = ~k
-                kg = k[perm]
-                perm = perm[_stable_sort_perm_by(kg)]
+                perm = _value_pass(s, _string_chunk_key(s, c), desc, perm)
         else:
-            k = _order_key_u64(s)
-            if desc:
-                k = ~k
-            kg = k[perm]
-            perm = perm[_stable_sort_perm_by(kg)]
+            perm = _value_pass(s, _order_key_u64(s), desc, perm)
         if s.validity is not None:
             # null-placement pass dominates value order (applied after):
             # encode so rows that should sort first get the smaller key

@@ -156,10 +156,11 @@ def _eq_literal(s: Series, value: str, ci: bool) -> Series:
 
 
 def _like_regex(s: Series, pattern: str, ci: bool) -> Series:
+    # `%` and `_` match newlines too, and the whole value must match
     rx = re.escape(pattern).replace("%", ".*").replace("_", ".")
-    rx = re.compile(f"^{rx}$", re.IGNORECASE if ci else 0)
+    rx = re.compile(rx, re.DOTALL | (re.IGNORECASE if ci else 0))
     vals = _pylist_str(s.cpu())
-    out = torch.tensor([False if v is None else rx.match(v) is not None
+    out = torch.tensor([False if v is None else rx.fullmatch(v) is not None
                         for v in vals], dtype=torch.bool).to(s.device)
     return _bool_out(s, out)
 
@@ -207,21 +208,28 @@ def length_bytes(s: Series) -> Series:
 
 
 def substr(s: Series, start: int, length: Optional[int]) -> Series:
-    """Byte-offset substring (ASCII-correct; round-1 simplification)."""
+    """`length` characters from character `start` (0-based), to the end when
+    `length` is None.  STRING columns count UTF-8 code points, BINARY
+    columns bytes.  A start past the end, or `length == 0`, gives ""; a
+    negative `start` or `length` raises ValueError."""
+    if start < 0 or (length is not None and length < 0):
+        raise ValueError(
+            f"substr: start and length must be >= 0, got start={start}, "
+            f"length={length}")
     d = _dict_map(s, lambda v: substr(v, start, length))
     if d is not None:
         return d
     if _is_gpu(s):
         new_off, new_bytes = native_required().str_substr(
-            s.offsets, s.data, start, -1 if length is None else length)
+            s.offsets, s.data, start, -1 if length is None else length,
+            s.dtype.kind == TypeKind.STRING)
         return Series(s.name, s.dtype, data=new_bytes, offsets=new_off,
                       validity=s.validity)
     vals = _pylist_str(s)
-    end = None if length is None else None
     out = [None if v is None else
            (v[start:] if length is None else v[start:start + length])
            for v in vals]
-    return Series.from_pylist(s.name, out, DataType.string()) \
+    return Series.from_pylist(s.name, out, s.dtype) \
         .with_validity(s.validity)
 
 
@@ -233,11 +241,18 @@ def _map_python(s: Series, f) -> Series:
     return res.to(s.device) if s.is_gpu() else res
 
 
+def _all_ascii(s: Series) -> bool:
+    """One device reduction: the byte-parallel case kernel maps ASCII
+    letters only, and Unicode case mapping can change a value's length, so
+    a column with any byte >= 0x80 takes the host path."""
+    return not bool((s.data >= 0x80).any().item())
+
+
 def lower(s: Series) -> Series:
     d = _dict_map(s, lambda v: lower(v))
     if d is not None:
         return d
-    if _is_gpu(s):
+    if _is_gpu(s) and _all_ascii(s):
         out = native_required().str_case(s.offsets, s.data, 0)
         return Series(s.name, s.dtype, data=out, offsets=s.offsets,
                       validity=s.validity)
@@ -248,7 +263,7 @@ def upper(s: Series) -> Series:
     d = _dict_map(s, lambda v: upper(v))
     if d is not None:
         return d
-    if _is_gpu(s):
+    if _is_gpu(s) and _all_ascii(s):
         out = native_required().str_case(s.offsets, s.data, 1)
         return Series(s.name, s.dtype, data=out, offsets=s.offsets,
                       validity=s.validity)
@@ -293,8 +308,11 @@ def capitalize(s: Series) -> Series:
 def concat_str(parts: List[Series]) -> Series:
     """Row-wise string concatenation."""
     parts = [p.dict_decode() for p in parts]
-    n = max(len(p) for p in parts)
-    parts = [p.broadcast(n) if len(p) == 1 else p for p in parts]
+    # length-1 parts broadcast to the length of the others (which may be 0)
+    lens = {len(p) for p in parts if len(p) != 1}
+    assert len(lens) <= 1, f"concat_str: lengths differ: {sorted(lens)}"
+    n = lens.pop() if lens else 1
+    parts = [p.broadcast(n) if len(p) != n else p for p in parts]
     if _is_gpu(parts[0]):
         offs = [p.offsets for p in parts]
         datas = [p.data for p in parts]
@@ -331,6 +349,9 @@ def right(s: Series, n: int) -> Series:
 
 
 def find(s: Series, pat: str) -> Series:
+    """Byte offset of the first match in the UTF-8 encoding, -1 if none
+    (what the reference's `str::find` and the HIP kernel return; not the
+    code-point index of Python's `str.find`)."""
     s = s.dict_decode()
     if _is_gpu(s):
         p = _bytes_tensor(pat.encode(), s.device)
@@ -338,8 +359,9 @@ def find(s: Series, pat: str) -> Series:
         return Series(s.name, DataType.int64(), data=out,
                       validity=s.validity)
     vals = _pylist_str(s)
-    out = torch.tensor([-1 if v is None else v.find(pat) for v in vals],
-                       dtype=torch.int64)
+    pb = pat.encode()
+    out = torch.tensor([-1 if v is None else v.encode().find(pb)
+                        for v in vals], dtype=torch.int64)
     return Series(s.name, DataType.int64(), data=out, validity=s.validity)
 
 

@@ -229,15 +229,7 @@ def expr_to_daft(e, binder: Optional[Binder]) -> Expression:
         return fns[e.part]()
     if isinstance(e, P.SubstringExpr):
         c = expr_to_daft(e.child, binder)
-        start = e.start.value if isinstance(e.start, P.Lit) else None
-        if start is None:
-            raise SQLPlanError("SUBSTRING start must be a literal")
-        length = None
-        if e.length is not None:
-            if not isinstance(e.length, P.Lit):
-                raise SQLPlanError("SUBSTRING length must be a literal")
-            length = int(e.length.value)
-        return c.str.substr(int(start) - 1, length)
+        return c.str.substr(*_substring_args(e.start, e.length, binder))
     if isinstance(e, P.FuncCall):
         return _bind_func(e, binder)
     if isinstance(e, (P.SubqueryExpr, P.InSubquery, P.ExistsExpr)):
@@ -282,10 +274,8 @@ def _bind_func(e: P.FuncCall, binder) -> Expression:
         from ..functions import coalesce
         return coalesce(*args)
     if name == "substr" or name == "substring":
-        start = int(_litval_num(e.args[1], binder)) - 1
-        length = int(_litval_num(e.args[2], binder)) if len(e.args) > 2 \
-            else None
-        return args[0].str.substr(start, length)
+        return args[0].str.substr(*_substring_args(
+            e.args[1], e.args[2] if len(e.args) > 2 else None, binder))
     if name == "concat":
         out = args[0]
         for a in args[1:]:
@@ -327,7 +317,23 @@ def _litval(e: Expression):
 def _litval_num(a, binder):
     if isinstance(a, P.Lit):
         return a.value
+    if isinstance(a, P.UnaryOp) and a.op == "neg":
+        return -_litval_num(a.child, binder)
     raise SQLPlanError("expected literal argument")
+
+
+def _substring_args(start, length, binder):
+    """SQL SUBSTRING(x, s, l) -> 0-based (start, length) for str.substr.
+    Positions are 1-based and the window [s, s + l) may begin before the
+    string: what lies before position 1 is cut off, as the SQL standard
+    says, so s < 1 gives start 0 and length max(0, l + s - 1)."""
+    s = int(_litval_num(start, binder))
+    n = None if length is None else int(_litval_num(length, binder))
+    if n is not None and n < 0:
+        raise SQLPlanError("SUBSTRING length must not be negative")
+    if s < 1:
+        return 0, None if n is None else max(0, n + s - 1)
+    return s - 1, n
 
 
 # ---------------------------------------------------------------------------
