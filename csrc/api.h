@@ -54,7 +54,14 @@ std::vector<Tensor> grouped_multi_agg(Tensor gids, int64_t num_groups,
                                       std::vector<OptTensor> valids,
                                       std::vector<int64_t> ops);
 
-// join (kernels.hip)
+// join (join.hip).  mode: 0 inner, 1 left, 2 semi, 3 anti.
+// direct-address: int32 table of rng slots, table[key - mn] = build row or
+// -1; returns {table, dup} where dup[0] != 0 reports duplicate build keys
+// (only looked for when check_dup).
+std::vector<Tensor> dense_join_build(Tensor keys, int64_t mn, int64_t rng,
+                                     bool check_dup);
+std::vector<Tensor> dense_join_probe(Tensor keys, OptTensor valid, int64_t mn,
+                                     Tensor table, int64_t mode);
 std::vector<Tensor> join_build(Tensor hashes);
 std::vector<Tensor> join_probe(
     Tensor table, Tensor next, Tensor probe_hashes, Tensor build_hashes,
@@ -62,7 +69,7 @@ std::vector<Tensor> join_probe(
     const std::vector<OptTensor>& off_l, const std::vector<OptTensor>& val_l,
     const std::vector<int64_t>& tags_r, const std::vector<Tensor>& data_r,
     const std::vector<OptTensor>& off_r, const std::vector<OptTensor>& val_r,
-    int64_t mode);
+    int64_t mode, bool need_matched);
 
 // sort (sort.hip)
 Tensor radix_argsort(Tensor keys);

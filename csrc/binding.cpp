@@ -18,6 +18,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "first-occurrence index per packed dense key");
   m.def("count_distinct_pairs", &count_distinct_pairs,
         "one-pass per-group distinct-value counts");
+  m.def("dense_join_build", &dense_join_build,
+        "direct-address join build -> (table, dup flag)");
+  m.def("dense_join_probe", &dense_join_probe,
+        "direct-address join probe -> (lidx, ridx)");
   m.def("join_build", &join_build, "bucket-chain hash join build");
   m.def("join_probe", &join_probe, "hash join probe -> (lidx, ridx, matched)");
   m.def("radix_argsort", &radix_argsort, "stable LSD radix argsort of u64");

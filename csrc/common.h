@@ -19,6 +19,13 @@ static inline int grid_1d(int64_t n, int block, int items_per_thread = 1) {
   return (int)work;
 }
 
+// power-of-2 hash table size at load factor <= 0.5 (groupby, join)
+static inline int64_t table_capacity(int64_t n) {
+  int64_t cap = 64;
+  while (cap < 2 * n) cap <<= 1;
+  return cap;
+}
+
 DEV_INLINE uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;

@@ -1,6 +1,6 @@
 // Core row-wise HIP kernels for gfx950: row hashing, stream compaction,
-// string gather, hash groupby, bucket-chain hash join, hash partitioning
-// (grouped aggregation lives in groupagg.hip).  MI355X-native design notes:
+// string gather, hash groupby, hash partitioning (grouped aggregation lives
+// in groupagg.hip, joins in join.hip).  MI355X-native design notes:
 //  * one thread per row, grid-stride, grids capped at 8 blocks/CU
 //  * hash tables are power-of-2 bucket arrays in HBM; inserts use one
 //    device-scope atomic each (no locks) — per-XCD L2 non-coherence is safe
@@ -341,12 +341,6 @@ __global__ void groupby_gather_ids_kernel(const int64_t* row_slot,
     gids[i] = (int64_t)slot_gid[row_slot[i]];
 }
 
-static int64_t table_capacity(int64_t n) {
-  int64_t cap = 64;
-  while (cap < 2 * n) cap <<= 1;
-  return cap;
-}
-
 std::vector<Tensor> groupby(Tensor hashes, const std::vector<int64_t>& tags,
                             const std::vector<Tensor>& datas,
                             const std::vector<OptTensor>& offsets,
@@ -480,147 +474,6 @@ Tensor dense_first_index(Tensor packed, int64_t rng, int64_t sentinel) {
                        first.data_ptr<int64_t>());
   }
   return first;
-}
-
-// ---------------------------------------------------------------------------
-// hash join: bucket-chain build + verified probe
-// ---------------------------------------------------------------------------
-
-__global__ void join_build_kernel(const uint64_t* hashes, int64_t n,
-                                  int64_t* heads, int64_t* next,
-                                  uint64_t mask) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    uint64_t b = hashes[i] & mask;
-    long long prev = atomicExch((unsigned long long*)&heads[b],
-                                (unsigned long long)i);
-    next[i] = prev;
-  }
-}
-
-std::vector<Tensor> join_build(Tensor hashes) {
-  auto dev = hashes.device();
-  int64_t n = hashes.numel();
-  auto opts64 = torch::dtype(torch::kInt64).device(dev);
-  int64_t cap = table_capacity(std::max<int64_t>(n, 1));
-  auto heads = torch::full({cap}, -1, opts64);
-  auto next = torch::full({std::max<int64_t>(n, 1)}, -1, opts64);
-  if (n > 0) {
-    int block = 256;
-    hipLaunchKernelGGL(join_build_kernel, dim3(grid_1d(n, block)),
-                       dim3(block), 0, cur_stream(),
-                       (const uint64_t*)hashes.data_ptr<int64_t>(), n,
-                       heads.data_ptr<int64_t>(), next.data_ptr<int64_t>(),
-                       (uint64_t)(cap - 1));
-  }
-  return {heads, next};
-}
-
-// mode: 0=inner, 1=left, 2=semi, 3=anti.  Two passes over the same chain
-// walk: FILL=false writes each probe row's output count, FILL=true writes the
-// index pairs at offs[i] (the exclusive scan of those counts).
-template <bool FILL>
-__global__ void join_probe_kernel(const int64_t* heads, const int64_t* next,
-                                  const uint64_t* ph, const uint64_t* bh,
-                                  const ColDesc* pc, const ColDesc* bc,
-                                  int ncols, int64_t np, uint64_t mask,
-                                  int mode, int32_t* counts,
-                                  const int32_t* offs, int64_t* lidx,
-                                  int64_t* ridx, bool* matched) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < np;
-       i += stride) {
-    uint64_t h = ph[i];
-    int64_t pos = FILL ? offs[i] : 0;
-    int64_t m = 0;
-    if (!row_has_null(pc, ncols, i)) {
-      int64_t j = heads[h & mask];
-      while (j != -1) {
-        if (bh[j] == h && row_eq(pc, bc, ncols, i, j, false)) {
-          ++m;
-          if (mode >= 2) break;  // semi/anti: existence only
-          if constexpr (FILL) {
-            lidx[pos] = i;
-            ridx[pos] = j;
-            matched[j] = true;
-            ++pos;
-          }
-        }
-        j = next[j];
-      }
-    }
-    if constexpr (FILL) {
-      if (mode == 1 && m == 0) {
-        lidx[pos] = i;
-        ridx[pos] = -1;
-      } else if (mode == 2 && m) {
-        lidx[pos] = i;
-      } else if (mode == 3 && !m) {
-        lidx[pos] = i;
-      }
-    } else {
-      int32_t c;
-      switch (mode) {
-        case 0: c = (int32_t)m; break;
-        case 1: c = (int32_t)(m ? m : 1); break;
-        case 2: c = m ? 1 : 0; break;
-        default: c = m ? 0 : 1; break;
-      }
-      counts[i] = c;
-    }
-  }
-}
-
-std::vector<Tensor> join_probe(
-    Tensor table, Tensor next, Tensor probe_hashes, Tensor build_hashes,
-    const std::vector<int64_t>& tags_l, const std::vector<Tensor>& data_l,
-    const std::vector<OptTensor>& off_l, const std::vector<OptTensor>& val_l,
-    const std::vector<int64_t>& tags_r, const std::vector<Tensor>& data_r,
-    const std::vector<OptTensor>& off_r, const std::vector<OptTensor>& val_r,
-    int64_t mode) {
-  auto dev = probe_hashes.device();
-  int64_t np = probe_hashes.numel();
-  int64_t nb = build_hashes.numel();
-  auto opts64 = torch::dtype(torch::kInt64).device(dev);
-  auto pdescs = pack_descs(tags_l, data_l, off_l, val_l);
-  auto bdescs = pack_descs(tags_r, data_r, off_r, val_r);
-  uint64_t mask = (uint64_t)table.numel() - 1;
-  auto counts = torch::zeros({std::max<int64_t>(np, 1)},
-                             torch::dtype(torch::kInt32).device(dev));
-  int block = 256;
-  if (np > 0) {
-    hipLaunchKernelGGL(join_probe_kernel<false>, dim3(grid_1d(np, block)),
-                       dim3(block), 0, cur_stream(),
-                       table.data_ptr<int64_t>(), next.data_ptr<int64_t>(),
-                       (const uint64_t*)probe_hashes.data_ptr<int64_t>(),
-                       (const uint64_t*)build_hashes.data_ptr<int64_t>(),
-                       (const ColDesc*)pdescs.data_ptr(),
-                       (const ColDesc*)bdescs.data_ptr(), (int)tags_l.size(),
-                       np, mask, (int)mode, counts.data_ptr<int32_t>(),
-                       nullptr, nullptr, nullptr, nullptr);
-  }
-  auto offs = torch::cumsum(counts, 0, torch::kInt32) - counts;
-  int64_t total = np > 0 ? counts.sum().item<int64_t>() : 0;
-  auto lidx = torch::empty({total}, opts64);
-  bool emit_ridx = mode < 2;
-  auto ridx = torch::empty({emit_ridx ? total : 0}, opts64);
-  auto matched = torch::zeros({std::max<int64_t>(nb, 1)},
-                              torch::dtype(torch::kBool).device(dev));
-  if (np > 0 && total > 0) {
-    hipLaunchKernelGGL(join_probe_kernel<true>, dim3(grid_1d(np, block)),
-                       dim3(block), 0, cur_stream(),
-                       table.data_ptr<int64_t>(), next.data_ptr<int64_t>(),
-                       (const uint64_t*)probe_hashes.data_ptr<int64_t>(),
-                       (const uint64_t*)build_hashes.data_ptr<int64_t>(),
-                       (const ColDesc*)pdescs.data_ptr(),
-                       (const ColDesc*)bdescs.data_ptr(), (int)tags_l.size(),
-                       np, mask, (int)mode, nullptr, offs.data_ptr<int32_t>(),
-                       lidx.data_ptr<int64_t>(),
-                       emit_ridx ? ridx.data_ptr<int64_t>() : nullptr,
-                       matched.data_ptr<bool>());
-  }
-  return {lidx, ridx, matched.slice(0, 0, nb)};
 }
 
 // ---------------------------------------------------------------------------

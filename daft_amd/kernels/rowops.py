@@ -504,14 +504,63 @@ def _pack_int_keys(lk, rk):
 
 
 _DENSE_JOIN_LIMIT = 1 << 31  # direct table cap: 2G slots (8 GB int32)
+# a table of up to this many slots per PROBE row is also admitted.  In time
+# the direct table beats the hash join up to at least 16 slots per probe row
+# (profiles/join_direct_address.md); 4 bounds the transient table at 16 B
+# per probe row
+_DENSE_PROBE_FACTOR = 4
+_JOIN_MODES = {"inner": 0, "left": 1, "semi": 2, "anti": 3}
+
+
+def _dense_eligible(n_l: int, n_r: int, rng: int) -> bool:
+    """Whether a direct-address table of `rng` slots pays for a join of
+    n_l probe rows against n_r build rows: sparse by at most 16x against
+    the build side (or small outright), or proportional to the probe."""
+    if rng <= 0 or rng > _DENSE_JOIN_LIMIT:
+        return False
+    return rng <= max(16 * n_r, 1 << 20) or rng <= _DENSE_PROBE_FACTOR * n_l
+
+
+def _dense_keys_native(s):
+    """Key tensor for the native kernels: int32/int64 as they are."""
+    d = s.data
+    if d.dtype not in (torch.int32, torch.int64):
+        d = d.to(torch.int64)
+    return d.contiguous()
+
+
+def _dense_key_join_native(l, r, how, mn, rng):
+    """GPU direct-address join (csrc/join.hip).  None on duplicate build
+    keys of a join that emits build rows."""
+    nat = native_required()
+    check_dup = how not in ("semi", "anti")
+    table, dup = nat.dense_join_build(_dense_keys_native(r), mn, rng,
+                                      check_dup)
+    if check_dup and bool(dup.item()):
+        return None  # duplicate build keys: hash join handles fan-out
+    mode = _JOIN_MODES["left" if how in ("right", "outer") else how]
+    lidx, ridx = nat.dense_join_probe(_dense_keys_native(l), l.validity, mn,
+                                      table, mode)
+    if how in ("right", "outer"):
+        hit = ridx >= 0
+        matched = torch.zeros(len(r), dtype=torch.bool, device=r.device)
+        matched[ridx[hit]] = True
+        if how == "right":
+            lidx, ridx = lidx[hit], ridx[hit]
+        unmatched = torch.nonzero(~matched).reshape(-1)
+        if unmatched.numel():
+            lidx = torch.cat([lidx, torch.full_like(unmatched, -1)])
+            ridx = torch.cat([ridx, unmatched])
+    return lidx, ridx
 
 
 def _dense_key_join(lk, rk, how):
     """Direct-address join: when the build side is a single no-null
     integer key whose values are unique and densely ranged (the PK-join
     shape — orderkey/partkey/suppkey in TPC-H), replace the hash table
-    with an addressed row array.  Probe is then one gather + a compare:
-    no hashing, no chain walks, no count/fill passes.  Returns None to
+    with an addressed row array.  Probe is then one key load + one table
+    lookup per row: no hashing, no chain walks.  On the GPU this runs in
+    csrc/join.hip; the torch code below is the CPU path.  Returns None to
     fall back to the bucket-chain hash join."""
     if len(lk) != 1 or len(rk) != 1:
         return None
@@ -531,15 +580,13 @@ def _dense_key_join(lk, rk, how):
     if n_r == 0 or n_l == 0:
         return None
     dev = r.device
-    rdata = r.data.to(torch.int64)
-    mn = int(rdata.min().item())
-    mx = int(rdata.max().item())
+    mn, mx = (int(v) for v in torch.stack(torch.aminmax(r.data)).tolist())
     rng = mx - mn + 1
-    # 16x sparsity still wins: the direct table costs rng x 4B of HBM
-    # (transient) and one memset, vs a chained hash build + 2-pass probe
-    if rng <= 0 or rng > max(16 * n_r, 1 << 20) or \
-            rng > _DENSE_JOIN_LIMIT:
+    if not _dense_eligible(n_l, n_r, rng):
         return None
+    if _is_gpu(r) and n_r < (1 << 31):
+        return _dense_key_join_native(l, r, how, mn, rng)
+    rdata = r.data.to(torch.int64)
     idx_t = torch.int32 if n_r < (1 << 31) else torch.int64
     table = torch.full((rng,), -1, dtype=idx_t, device=dev)
     rows = torch.arange(n_r, dtype=idx_t, device=dev)
@@ -605,11 +652,11 @@ def _gpu_join(lk, rk, how):
     table, nxt = nat.join_build(rh)
     tags_l, data_l, off_l, val_l = _descs(lk)
     tags_r, data_r, off_r, val_r = _descs(rk)
-    mode = {"inner": 0, "left": 1, "semi": 2, "anti": 3,
-            "right": 0, "outer": 1}[how]
+    mode = _JOIN_MODES[{"right": "inner", "outer": "left"}.get(how, how)]
+    need_matched = how in ("right", "outer")  # only they read matched[]
     lidx, ridx, matched = nat.join_probe(
         table, nxt, lh, rh, tags_l, data_l, off_l, val_l,
-        tags_r, data_r, off_r, val_r, mode)
+        tags_r, data_r, off_r, val_r, mode, need_matched)
     if how in ("right", "outer"):
         unmatched = torch.nonzero(~matched.to(torch.bool)).reshape(-1)
         if unmatched.numel():

@@ -19,6 +19,7 @@ setup(
                 "csrc/binding.cpp",
                 "csrc/kernels.hip",
                 "csrc/groupagg.hip",
+                "csrc/join.hip",
                 "csrc/sort.hip",
                 "csrc/strings.hip",
                 "csrc/multimodal.hip",
