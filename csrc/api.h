@@ -128,3 +128,10 @@ std::vector<Tensor> str_concat(const std::vector<Tensor>& offsets,
 Tensor str_char_length(Tensor offsets, Tensor bytes);
 Tensor string_compare(Tensor a_off, Tensor a_bytes, Tensor b_off,
                       Tensor b_bytes);
+
+// regex / LIKE by DFA tables (regex.hip).  table: int16 [n_states,
+// n_classes], byte_class: uint8 [256], flags: uint8 [n_states] (1 matched,
+// 2 matches at end of row, 4 dead); all three are staged in LDS.
+Tensor regex_match(Tensor offsets, Tensor bytes, Tensor table,
+                   Tensor byte_class, Tensor flags, int64_t n_classes,
+                   int64_t start);

@@ -153,7 +153,7 @@ from .strings_extra import (  # noqa: E402,F401
     to_upper_kebab_case, to_camel_case, to_upper_camel_case,
     to_title_case, normalize, concat_ws, format, ascii_func, chr_func,
     space, translate, replace, split_part, substring_index,
-    count_matches, regexp, regexp_count, regexp_extract,
+    count_matches, regexp, regexp_match, regexp_count, regexp_extract,
     regexp_extract_all, regexp_replace, regexp_split,
     levenshtein_distance, damerau_levenshtein_distance,
     hamming_distance_str, jaro_similarity, jaro_winkler_similarity,

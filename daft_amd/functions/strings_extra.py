@@ -198,6 +198,14 @@ def regexp(expr, pattern: str):
     return _e(expr).str.match(pattern)
 
 
+def regexp_match(expr, pattern: str):
+    """True where `pattern` matches somewhere in the value (`re.search`)."""
+    if not isinstance(pattern, str):
+        raise TypeError("regexp_match: pattern must be a str, got "
+                        f"{type(pattern).__name__}")
+    return _e(expr).str.match(pattern)
+
+
 def regexp_count(expr, pattern: str):
     p = _re.compile(pattern)
     return _host_map("regexp_count", lambda v: len(p.findall(v)),

@@ -4,6 +4,7 @@ predicates run as HIP kernels over offsets+bytes on GPU, CPU falls back to
 python/numpy for the test tier)."""
 from __future__ import annotations
 
+import functools
 import re
 from typing import List, Optional
 
@@ -12,7 +13,7 @@ import torch
 
 from ..schema import DataType, TypeKind
 from ..series import Series
-from . import _is_gpu, native_required
+from . import _is_gpu, native_required, regex_dfa
 
 
 def _bytes_tensor(pat: bytes, device) -> torch.Tensor:
@@ -94,8 +95,9 @@ def like(s: Series, pattern: str, case_insensitive: bool = False) -> Series:
     """SQL LIKE: % = any run, _ = any single char.
 
     Patterns without `_` (every TPC-H LIKE) run as a single ordered
-    multi-substring HIP kernel on GPU; general patterns fall back to a host
-    regex pass."""
+    multi-substring HIP kernel on GPU; patterns with `_` and ILIKE run the
+    DFA kernel on GPU (csrc/regex.hip), or a host regex pass where that
+    does not apply."""
     d = _dict_pred(s, lambda v: like(v, pattern, case_insensitive))
     if d is not None:
         return d
@@ -122,7 +124,7 @@ def like(s: Series, pattern: str, case_insensitive: bool = False) -> Series:
             [False if v is None else _ordered_match(v, needles, ap, asfx)
              for v in vals], dtype=torch.bool)
         return _bool_out(s, out)
-    return _like_regex(s, pattern, case_insensitive)
+    return _like_general(s, pattern, case_insensitive)
 
 
 def _ordered_match(v: str, needles: List[str], anchored_prefix: bool,
@@ -148,32 +150,73 @@ def _ordered_match(v: str, needles: List[str], anchored_prefix: bool,
 
 def _eq_literal(s: Series, value: str, ci: bool) -> Series:
     if ci:
-        return _like_regex(s, value, True)
+        return _like_general(s, value, True)
     from . import compare_op
     lit = Series.from_pylist(s.name, [value], DataType.string(),
                              device=s.device)
     return compare_op(s, lit.broadcast(len(s)), "eq")
 
 
+def _host_regex_pred(s: Series, rx, full: bool) -> Series:
+    """Host path of every regex predicate: one `re` call per row."""
+    hit = rx.fullmatch if full else rx.search
+    vals = _pylist_str(s.cpu())
+    out = torch.tensor([False if v is None else hit(v) is not None
+                        for v in vals], dtype=torch.bool).to(s.device)
+    return _bool_out(s, out)
+
+
+@functools.lru_cache(maxsize=64)
+def _device_tables(prog, device: str):
+    return tuple(torch.from_numpy(a).to(device)
+                 for a in (prog.table, prog.byte_class, prog.flags))
+
+
+def _device_dfa_pred(s: Series, pattern: str, build) -> Optional[Series]:
+    """Run `build()`'s DFA over a device column with the HIP kernel.  None
+    when the column is not on the device, the pattern is outside the DFA
+    engine, or the program is ASCII-only and pattern or column is not."""
+    if not _is_gpu(s):
+        return None
+    try:
+        prog = build()
+    except regex_dfa.Unsupported:
+        return None
+    if prog.needs_ascii and not (pattern.isascii() and _all_ascii(s)):
+        return None
+    table, byte_class, flags = _device_tables(prog, str(s.device))
+    out = native_required().regex_match(
+        s.offsets, s.data, table, byte_class, flags, prog.n_classes,
+        prog.start)
+    return _bool_out(s, out)
+
+
+def _like_general(s: Series, pattern: str, ci: bool) -> Series:
+    """LIKE with `_`, and every ILIKE: DFA kernel on the device, else the
+    host regex."""
+    d = _device_dfa_pred(s, pattern,
+                         lambda: regex_dfa.like_program(pattern, ci))
+    return d if d is not None else _like_regex(s, pattern, ci)
+
+
 def _like_regex(s: Series, pattern: str, ci: bool) -> Series:
     # `%` and `_` match newlines too, and the whole value must match
     rx = re.escape(pattern).replace("%", ".*").replace("_", ".")
     rx = re.compile(rx, re.DOTALL | (re.IGNORECASE if ci else 0))
-    vals = _pylist_str(s.cpu())
-    out = torch.tensor([False if v is None else rx.fullmatch(v) is not None
-                        for v in vals], dtype=torch.bool).to(s.device)
-    return _bool_out(s, out)
+    return _host_regex_pred(s, rx, True)
 
 
 def regexp_match(s: Series, pattern: str) -> Series:
+    """`re.search` semantics.  Device columns run the DFA kernel where the
+    pattern compiles to one (see regex_dfa.py); everything else is `re`."""
     d = _dict_pred(s, lambda v: regexp_match(v, pattern))
     if d is not None:
         return d
-    rx = re.compile(pattern)
-    vals = _pylist_str(s.cpu())
-    out = torch.tensor([False if v is None else rx.search(v) is not None
-                        for v in vals], dtype=torch.bool).to(s.device)
-    return _bool_out(s, out)
+    d = _device_dfa_pred(s, pattern,
+                         lambda: regex_dfa.compile(pattern, "search"))
+    if d is not None:
+        return d
+    return _host_regex_pred(s, re.compile(pattern), False)
 
 
 # --- length / manipulation ------------------------------------------------

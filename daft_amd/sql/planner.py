@@ -296,6 +296,16 @@ def _bind_func(e: P.FuncCall, binder) -> Expression:
         return args[0].fill_null(args[1])
     if name in simple:
         return simple[name](*args)
+    if name == "regexp_match":
+        from ..expressions.expressions import Literal
+        from ..functions import regexp_match
+        if len(args) != 2:
+            raise SQLPlanError("regexp_match() takes a column and a pattern")
+        pat = args[1]._node
+        if not isinstance(pat, Literal) or not isinstance(pat.value, str):
+            raise SQLPlanError(
+                "regexp_match() pattern must be a string literal")
+        return regexp_match(args[0], pat.value)
     # fall back to the free-function registry (daft.functions parity
     # surface: sin/levenshtein_distance/to_snake_case/...)
     from .. import functions as F

@@ -22,6 +22,7 @@ setup(
                 "csrc/join.hip",
                 "csrc/sort.hip",
                 "csrc/strings.hip",
+                "csrc/regex.hip",
                 "csrc/multimodal.hip",
                 "csrc/fusedexpr.hip",
                 "csrc/fusedjit.hip",
