@@ -1,15 +1,17 @@
-// Fused expression evaluation for gfx950 (CDNA4).
+// Fused expression evaluation for gfx950 (CDNA4): the interpreter.
 //
 // One kernel evaluates an entire projection / predicate list: a postfix
 // program over (value f64, valid bool) stack slots, one thread per row,
-// grid-stride.  Replaces chains of per-node torch elementwise kernels
-// (the reference evaluates at eval_expression_list granularity,
-// /root/reference/src/daft-recordbatch/src/lib.rs:1623; rocprof r01 showed
-// at::native elementwise/index kernels were ~half of remaining GPU time).
+// grid-stride.  It is the fallback for the hipRTC path (fusedjit.hip) and
+// replaces chains of per-node torch elementwise kernels.
 //
-// All arithmetic runs in f64 (exact for ints < 2^53; the Python compiler
-// bails out on anything wider or non-numeric).  Decimal(p<=18) columns are
-// loaded as scaled int64 and multiplied by 10^-scale.  AND/OR use Kleene
+// The stack is f64.  The Python compiler (daft_amd/kernels/fused.py) only
+// emits programs whose integer values provably stay within +-2^53, where
+// f64 is exact; it bails on int64/uint64/timestamp columns.  OP_CAST rounds
+// to f32 or wraps to a narrower integer width wherever the expression's
+// dtype demands it.  Decimal(p<=18) columns are loaded as scaled int64 and
+// DIVIDED by 10^scale (an exact f64 constant, so the quotient is correctly
+// rounded; multiplying by the inexact 10^-scale is not).  AND/OR use Kleene
 // three-valued logic matching kernels.logical_op.
 #include "common.h"
 
@@ -29,7 +31,7 @@ struct FCol {
   const void* data;
   const bool* valid;
   int64_t code;   // 0=f64 1=f32 2=i64 3=i32 4=i16 5=i8 6=bool/u8 7=u32 8=u64
-  double scale;   // applied after load (decimal descale); 1.0 default
+  double scale;   // load divides by this (decimal 10^scale); 1.0 default
 };
 
 struct FOut {
@@ -46,6 +48,7 @@ enum : int32_t {
   OP_AND = 12, OP_OR = 13, OP_NOT = 14, OP_NEG = 15,
   OP_ISNULL = 16, OP_NOTNULL = 17, OP_FILLNULL = 18, OP_SELECT = 19,
   OP_STORE = 20,
+  OP_CAST = 21,   // arg: 1=f32 3=i32 4=i16 5=i8 6=u8 7=u32 9=bool 10=u16
 };
 
 #define FE_STACK 12
@@ -62,9 +65,25 @@ DEV_INLINE double fe_load(const FCol& c, int64_t i, bool* valid) {
     case 5: v = (double)((const int8_t*)c.data)[i]; break;
     case 6: v = (double)((const uint8_t*)c.data)[i]; break;
     case 7: v = (double)((const uint32_t*)c.data)[i]; break;
-    case 8: v = (double)(int64_t)((const uint64_t*)c.data)[i]; break;
+    case 8: v = (double)((const uint64_t*)c.data)[i]; break;
   }
-  return v * c.scale;
+  return v / c.scale;
+}
+
+// v is integral and within +-2^53 for the integer codes (compiler
+// guarantee), so the int64 conversion is exact and the narrowing wraps.
+DEV_INLINE double fe_cast(double v, int code) {
+  switch (code) {
+    case 1: return (double)(float)v;
+    case 3: return (double)(int32_t)(int64_t)v;
+    case 4: return (double)(int16_t)(int64_t)v;
+    case 5: return (double)(int8_t)(int64_t)v;
+    case 6: return (double)(uint8_t)(int64_t)v;
+    case 7: return (double)(uint32_t)(int64_t)v;
+    case 9: return v != 0.0 ? 1.0 : 0.0;
+    case 10: return (double)(uint16_t)(int64_t)v;
+  }
+  return v;
 }
 
 template <bool HV>
@@ -172,6 +191,11 @@ __global__ void fused_eval_kernel(const int32_t* __restrict__ prog,
         case OP_NEG:
 #pragma unroll
           for (int r = 0; r < R; ++r) st[sp - 1][r] = -st[sp - 1][r];
+          break;
+        case OP_CAST:
+#pragma unroll
+          for (int r = 0; r < R; ++r)
+            st[sp - 1][r] = fe_cast(st[sp - 1][r], arg);
           break;
         case OP_ISNULL:
 #pragma unroll

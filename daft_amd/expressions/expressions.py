@@ -162,6 +162,9 @@ class BinaryOp(ExprNode):
             return Field(lf.name, DataType.float64())
         if self.op == "sub" and lf.dtype.kind == rf.dtype.kind == TypeKind.DATE:
             return Field(lf.name, DataType.duration("us"))
+        if self.op == "sub" and \
+                lf.dtype.kind == rf.dtype.kind == TypeKind.TIMESTAMP:
+            return Field(lf.name, DataType.duration(lf.dtype.timeunit))
         if lf.dtype.is_temporal():
             return Field(lf.name, lf.dtype)
         if lf.dtype.is_string() and self.op == "add":

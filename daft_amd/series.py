@@ -28,6 +28,18 @@ import torch
 from .schema import DataType, Field, TypeKind, from_torch_dtype, supertype
 
 _EPOCH = _dt.date(1970, 1, 1)
+_EPOCH_DT = _dt.datetime(1970, 1, 1)
+_EPOCH_UTC = _dt.datetime(1970, 1, 1, tzinfo=_dt.timezone.utc)
+_US = _dt.timedelta(microseconds=1)
+_US_PER = {"s": 10**6, "ms": 10**3, "us": 1}
+
+
+def datetime_to_units(v: "_dt.datetime", timeunit: str) -> int:
+    """Exact count of `timeunit` since the epoch (floored for s/ms).  An
+    aware datetime is taken at its UTC instant.  Integer timedelta
+    division: total_seconds() * 1e6 is off by one for ~2% of values."""
+    us = (v - (_EPOCH_UTC if v.tzinfo is not None else _EPOCH_DT)) // _US
+    return us * 1000 if timeunit == "ns" else us // _US_PER[timeunit]
 
 
 def _null_and(a: Optional[torch.Tensor], b: Optional[torch.Tensor]):
@@ -656,14 +668,12 @@ def _from_pylist_typed(name: str, values: list, dtype: DataType) -> Series:
                       data=torch.tensor(days, dtype=torch.int32),
                       validity=validity)
     if k == TypeKind.TIMESTAMP:
-        mult = {"s": 1, "ms": 10**3, "us": 10**6, "ns": 10**9}[dtype.timeunit]
         out = []
         for v in values:
             if v is None:
                 out.append(0)
             elif isinstance(v, _dt.datetime):
-                out.append(int(v.timestamp() * mult) if v.tzinfo else
-                           int((v - _dt.datetime(1970, 1, 1)).total_seconds() * mult))
+                out.append(datetime_to_units(v, dtype.timeunit))
             else:
                 out.append(int(v))
         return Series(name, dtype, data=torch.tensor(out, dtype=torch.int64),
