@@ -820,7 +820,7 @@ class Expression:
         from .. import kernels
 
         def _h(s: Series, sd) -> Series:
-            h = kernels.hash_columns([s], sd)
+            h = kernels.hash_values([s], sd)
             return Series(s.name, DataType.uint64(), data=h.view(torch.uint64))
         return Expression(ScalarFn("hash", _h, [self._node],
                                    DataType.uint64(), (seed,)))

@@ -311,7 +311,7 @@ def partition_hours(x):
 def partition_iceberg_bucket(x, n: int):
     def run(s: Series) -> Series:
         from ..kernels import rowops
-        h = rowops.hash_columns([s])
+        h = rowops.hash_values([s])
         out = torch.remainder(h.abs(), n).to(torch.int32)
         return Series(s.name, DataType.int32(), data=out,
                       validity=s.validity)

@@ -194,7 +194,7 @@ def random_int(expr, low: int = 0, high: int = 2**31 - 1):
     from ..kernels import rowops
 
     def run(s: Series) -> Series:
-        h = rowops.hash_columns([s]).abs()
+        h = rowops.hash_values([s]).abs()
         out = low + (h % max(1, high - low))
         return Series(s.name, DataType.int64(), data=out,
                       validity=s.validity)

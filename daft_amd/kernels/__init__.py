@@ -991,6 +991,6 @@ def _null_and(a, b):
 # row-wise kernels (hash/groupby/join/sort/partition) — imported last to
 # close the module cycle (rowops uses the descriptor helpers above)
 from .rowops import (  # noqa: E402
-    argsort_multi, groupby, grouped_agg, hash_columns, join,
+    argsort_multi, groupby, grouped_agg, hash_columns, hash_values, join,
     partition_by_hash, partition_by_value, partition_random,
 )

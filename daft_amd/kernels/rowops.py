@@ -43,6 +43,15 @@ def hash_columns(series: Sequence[Series], seed: int = 0) -> torch.Tensor:
     return _cpu_hash_columns(series, seed)
 
 
+def hash_values(series: Sequence[Series], seed: int = 0) -> torch.Tensor:
+    """The user-visible row hash (Series.hash, Expression.hash): a function
+    of the values alone, so dictionary-encoded strings are decoded first.
+    Grouping, joins and partitioning call hash_columns, which may hash a
+    dictionary column by its codes: those hashes never leave one operator."""
+    return hash_columns([s.dict_decode() if s.is_dict() else s
+                         for s in series], seed)
+
+
 def _splitmix64_np(x: np.ndarray) -> np.ndarray:
     x = x.astype(np.uint64, copy=True)
     with np.errstate(over="ignore"):
@@ -62,6 +71,28 @@ def _fnv1a_bytes(b: bytes) -> int:
     return h
 
 
+def _hash_bytes_np(off: np.ndarray, buf: np.ndarray) -> np.ndarray:
+    """hash_bytes_dev (csrc/common.h) for every row of an offsets+bytes
+    column: 8-byte little-endian words through splitmix64, the byte length
+    folded into the start value, a zero-padded word for the tail.  One
+    numpy pass per word index over the rows that still have bytes left."""
+    start = off[:-1].astype(np.int64)
+    ln = (off[1:] - off[:-1]).astype(np.int64)
+    h = np.uint64(0xcbf29ce484222325) ^ ln.astype(np.uint64)
+    if not len(ln):
+        return h
+    padded = np.concatenate([buf, np.zeros(8, dtype=np.uint8)])
+    lane = np.arange(8, dtype=np.int64)
+    for w in range((int(ln.max()) + 7) // 8):
+        rows = np.flatnonzero(ln > 8 * w)
+        left = ln[rows] - 8 * w
+        b = padded[(start[rows] + 8 * w)[:, None] + lane]
+        b = np.where(lane[None, :] < left[:, None], b, np.uint8(0))
+        word = np.ascontiguousarray(b).view("<u8").reshape(-1)
+        h[rows] = _splitmix64_np(h[rows] ^ word)
+    return h
+
+
 _NULL_HASH = np.uint64(0x9E3779B97F4A7C15)
 
 
@@ -73,18 +104,15 @@ def _phys_float(dt: DataType) -> bool:
 
 def _cpu_hash_columns(series: Sequence[Series], seed: int) -> torch.Tensor:
     n = len(series[0])
-    acc = np.full(n, np.uint64(seed) + np.uint64(0x8445D61A4E774912),
+    # same bits as row_hash in csrc/row_ops.h; the seed is taken mod 2^64
+    acc = np.full(n, (int(seed) + 0x8445D61A4E774912) & 0xFFFFFFFFFFFFFFFF,
                   dtype=np.uint64)
     for s in series:
         if s.is_dict():
             s = s.dict_decode()
         k = s.dtype.kind
         if k in (TypeKind.STRING, TypeKind.BINARY):
-            off = s.offsets.numpy()
-            buf = s.data.numpy().tobytes()
-            h = np.fromiter(
-                (_fnv1a_bytes(buf[off[i]:off[i + 1]]) for i in range(n)),
-                dtype=np.uint64, count=n)
+            h = _hash_bytes_np(s.offsets.numpy(), s.data.numpy())
         else:
             d = s.data
             if d.dtype == torch.bool:
@@ -98,6 +126,9 @@ def _cpu_hash_columns(series: Sequence[Series], seed: int) -> torch.Tensor:
             else:
                 raw = d.to(torch.int64).numpy() if d.dtype != torch.uint64 \
                     else d.view(torch.int64).numpy()
+                if d.element_size() < 8:
+                    # 1/2/4-byte values are zero-extended (TAG_W1/W2/W4)
+                    raw = raw & ((1 << (8 * d.element_size())) - 1)
             h = _splitmix64_np(raw.view(np.uint64) if raw.dtype == np.int64
                                else raw.astype(np.uint64))
         if s.validity is not None:
@@ -775,7 +806,13 @@ def _order_key_u64(s: Series) -> torch.Tensor:
     if k == TypeKind.BOOL:
         return d.to(torch.int64)
     if _phys_float(s.dtype):
-        bits = d.to(torch.float64).view(torch.int64)
+        # every NaN is one key above +inf, and -0.0 ties with +0.0 (the
+        # canon_f64_bits rules grouping uses)
+        f = d.to(torch.float64)
+        f = torch.where(f == 0.0, torch.zeros_like(f), f)
+        bits = f.view(torch.int64)
+        bits = torch.where(f != f,
+                           torch.full_like(bits, 0x7FF8000000000000), bits)
         neg = bits < 0
         flipped = torch.where(neg, ~bits, bits ^ _SIGN64)
         return flipped

@@ -551,7 +551,7 @@ class Series:
     # ------------------------------------------------------------------
     def hash(self, seed: int = 0) -> torch.Tensor:
         from . import kernels
-        return kernels.hash_columns([self], seed)
+        return kernels.hash_values([self], seed)
 
     def argsort(self, descending: bool = False,
                 nulls_first: bool = False) -> torch.Tensor:
