@@ -78,6 +78,13 @@ Tensor string_chunk_key(Tensor offsets, Tensor bytes, int64_t chunk);
 // partition (kernels.hip)
 Tensor u64_mod(Tensor hashes, int64_t n_partitions);
 
+// stable one-pass partitioner (partition.hip).  Partition id of row i is
+// hashes[i] % P in unsigned 64-bit arithmetic, or splitmix64(hashes[i]) % P
+// when remix; 1 <= P <= 256.  Returns {perm int64[n], counts int64[P]}:
+// perm lists the rows of partition 0 in ascending order, then partition 1..
+std::vector<Tensor> hash_partition(Tensor hashes, int64_t num_partitions,
+                                   bool remix);
+
 // multimodal (multimodal.hip)
 Tensor simhash(Tensor offsets, Tensor bytes, int64_t ngram_size);
 Tensor minhash(Tensor offsets, Tensor bytes, int64_t num_hashes,

@@ -28,6 +28,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("string_chunk_key", &string_chunk_key,
         "big-endian 8-byte chunk keys for string sorting");
   m.def("u64_mod", &u64_mod, "unsigned modulo for hash partitioning");
+  m.def("hash_partition", &hash_partition,
+        "stable one-pass hash partition -> (perm, counts)");
   m.def("simhash", &simhash);
   m.def("minhash", &minhash, "word-ngram MinHash signatures (wave/row)");
   m.def("hll_update", &hll_update, "HyperLogLog register updates");

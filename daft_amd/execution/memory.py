@@ -6,9 +6,11 @@ its flight_shuffle_dirs disk spill tier).
 Round-1 scope: cached partition sets (collect() results, loaded tables)
 spill from HBM to host when a blocking operator's admission would exceed
 the limit; they transparently reload on next access (InMemorySourceOp moves
-partitions back to the execution device).  Operator-internal spill is a
-later-round item — with 288 GB of HBM per GPU, cached data dominates
-footprint at the benchmarked scales.
+partitions back to the execution device).  Operator-internal spill lives in
+the blocking operators themselves, against the same budget
+(physical/ops.py operator_budget): SortOp spills runs to host and
+range-buckets them, JoinOp spills a build side over the budget and joins it
+bucket by bucket (physical/grace_join.py); aggregates fold morsel by morsel.
 """
 from __future__ import annotations
 

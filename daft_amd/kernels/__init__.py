@@ -121,6 +121,11 @@ def take(s: Series, indices: torch.Tensor,
     k = s.dtype.kind
     n_out = int(indices.shape[0])
     dev = s.device
+    if len(s) == 0 and n_out:
+        # nothing to gather from: every index is the -1 null marker (the
+        # unmatched side of an outer join against an empty input); clamping
+        # it to row 0 would read past the end of the empty column
+        return full_null(s.name, s.dtype, n_out, dev)
     indices = indices.to(dev)
     if has_neg is None:
         has_neg = bool((indices < 0).any().item()) if n_out else False
@@ -992,5 +997,5 @@ def _null_and(a, b):
 # close the module cycle (rowops uses the descriptor helpers above)
 from .rowops import (  # noqa: E402
     argsort_multi, groupby, grouped_agg, hash_columns, hash_values, join,
-    partition_by_hash, partition_by_value, partition_random,
+    hash_partition, partition_by_hash, partition_by_value, partition_random,
 )

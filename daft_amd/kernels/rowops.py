@@ -1006,21 +1006,57 @@ def argsort_multi(keys: Sequence[Series], descending: Sequence[bool],
 # hash partitioning (feeds RCCL all-to-all; ref: recordbatch ops/partition.rs)
 # ---------------------------------------------------------------------------
 
+_NATIVE_PARTITIONS_MAX = 256    # one radix digit (csrc/partition.hip)
+
+
+def _splitmix64_torch(x: torch.Tensor) -> torch.Tensor:
+    """splitmix64 (csrc/common.h) on the int64 bit pattern of u64 values.
+    int64 add and multiply wrap like u64; only the right shifts need the
+    sign extension masked off."""
+    def shr(v, k):
+        return (v >> k) & ((1 << (64 - k)) - 1)
+    x = x + (0x9E3779B97F4A7C15 - (1 << 64))
+    x = (x ^ shr(x, 30)) * (0xBF58476D1CE4E5B9 - (1 << 64))
+    x = (x ^ shr(x, 27)) * (0x94D049BB133111EB - (1 << 64))
+    return x ^ shr(x, 31)
+
+
+def hash_partition(hashes: torch.Tensor, num_partitions: int,
+                   remix: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Stable grouping of rows by `hash % num_partitions` (unsigned 64-bit;
+    `splitmix64(hash) % num_partitions` when `remix`).  Returns (perm,
+    counts): `perm` lists the rows of partition 0 in ascending order, then
+    partition 1, ...; `counts[p]` = number of rows in partition p.
+
+    Up to 256 partitions the device path is the one-pass native partitioner
+    (csrc/partition.hip); above that it is u64_mod + a full radix sort."""
+    num_partitions = int(num_partitions)
+    if num_partitions < 1:
+        raise ValueError(f"num_partitions must be >= 1, got {num_partitions}")
+    if hashes.is_cuda:
+        if num_partitions <= _NATIVE_PARTITIONS_MAX:
+            perm, counts = native_required().hash_partition(
+                hashes, num_partitions, bool(remix))
+            return perm, counts
+        if remix:
+            hashes = _splitmix64_torch(hashes)
+        part = native_required().u64_mod(hashes, num_partitions)
+        counts = torch.bincount(part, minlength=num_partitions)
+        return _stable_sort_perm_by(part), counts
+    u = hashes.numpy().view(np.uint64)
+    if remix:
+        u = _splitmix64_np(u)
+    ids = (u % np.uint64(num_partitions)).astype(np.int64)
+    perm = np.argsort(ids, kind="stable").astype(np.int64)
+    counts = np.bincount(ids, minlength=num_partitions).astype(np.int64)
+    return torch.from_numpy(perm), torch.from_numpy(counts)
+
+
 def partition_by_hash(keys: Sequence[Series],
                       num_partitions: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Return (perm, counts): `perm` reorders rows grouped by partition id,
     `counts[p]` = number of rows in partition p."""
-    h = hash_columns(keys)
-    if h.is_cuda:
-        u = h
-        part = native_required().u64_mod(u, num_partitions)
-    else:
-        part = torch.from_numpy(
-            (h.numpy().view(np.uint64) % np.uint64(num_partitions))
-            .view(np.int64))
-    counts = torch.bincount(part, minlength=num_partitions)
-    perm = _stable_sort_perm_by(part)
-    return perm, counts
+    return hash_partition(hash_columns(keys), num_partitions, remix=False)
 
 
 def partition_random(n: int, num_partitions: int, seed: int,

@@ -147,6 +147,22 @@ def stream_host_batch(part, device, morsel: int):
         yield dev
 
 
+def operator_budget(ectx):
+    """HBM bytes a blocking operator (sort, join build) may hold before it
+    spills to host: the configured memory limit, else a third of the free
+    HBM on a GPU, else None (never spill)."""
+    cfg = getattr(ectx.ctx, "execution_config", None)
+    lim = getattr(cfg, "memory_limit_bytes", None) if cfg else None
+    if lim is not None:
+        return lim
+    if str(ectx.device).startswith("cuda"):
+        import torch as _t
+        if _t.cuda.is_available():
+            free, _tot = _t.cuda.mem_get_info(ectx.device)
+            return free // 3
+    return None
+
+
 _COPY_STREAMS: dict = {}
 
 
@@ -586,20 +602,8 @@ class SortOp(PhysicalOp):
         self.descending = descending
         self.nulls_first = nulls_first
 
-    def _budget(self, ectx):
-        cfg = getattr(ectx.ctx, "execution_config", None)
-        lim = getattr(cfg, "memory_limit_bytes", None) if cfg else None
-        if lim is not None:
-            return lim
-        if str(ectx.device).startswith("cuda"):
-            import torch as _t
-            if _t.cuda.is_available():
-                free, _tot = _t.cuda.mem_get_info(ectx.device)
-                return free // 3
-        return None
-
     def execute(self, ectx) -> BatchIter:
-        budget = self._budget(ectx)
+        budget = operator_budget(ectx)
         runs: List[RecordBatch] = []
         spilled: List[RecordBatch] = []
         acc = 0
@@ -740,9 +744,50 @@ class JoinOp(PhysicalOp):
         self.right_on = right_on
         self.how = how
         self.right_cols = right_cols  # (src_name, out_name)
+        # stats of the last run when it took the out-of-core grace path
+        # (physical/grace_join.py); None when the build side stayed in HBM
+        self.grace_stats: Optional[dict] = None
+
+    def _collect_build(self, ectx, budget):
+        """Pull the build side batch by batch.  Within the operator budget
+        this is _materialize_child and returns (batch, None).  The first
+        time the running size exceeds the budget, what has accumulated
+        moves to host, the rest of the child drains to host, and the
+        result is (None, host runs) for the grace path."""
+        batches: List[RecordBatch] = []
+        spilled: Optional[List[RecordBatch]] = None
+        acc = 0
+        for rb in self.children[1].execute_tracked(ectx):
+            if spilled is not None:
+                if len(rb):
+                    spilled.append(rb.cpu())
+                continue
+            batches.append(rb)
+            acc += rb.size_bytes()
+            if budget is not None and acc > budget:
+                spilled = [b.cpu() for b in batches if len(b)]
+                batches = []
+        if spilled is not None:
+            return None, spilled
+        if not batches:
+            return RecordBatch.empty(self.children[1].schema,
+                                     device=ectx.device), None
+        if len(batches) == 1:
+            return batches[0], None
+        ectx.memory.admit(acc, ectx.device)
+        return RecordBatch.concat(batches), None
 
     def execute(self, ectx) -> BatchIter:
-        right = self._materialize_child(ectx, 1)
+        self.grace_stats = None
+        if self.how == "cross":
+            right = self._materialize_child(ectx, 1)
+        else:
+            budget = operator_budget(ectx)
+            right, spilled = self._collect_build(ectx, budget)
+            if spilled is not None:
+                from .grace_join import run_grace_join
+                yield from run_grace_join(self, ectx, spilled, budget)
+                return
         rkeys = [e.evaluate(right) for e in self.right_on]
 
         if self.how == "cross":

@@ -21,6 +21,7 @@ setup(
                 "csrc/groupagg.hip",
                 "csrc/join.hip",
                 "csrc/sort.hip",
+                "csrc/partition.hip",
                 "csrc/strings.hip",
                 "csrc/regex.hip",
                 "csrc/multimodal.hip",
