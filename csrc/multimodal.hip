@@ -86,9 +86,12 @@ __global__ void minhash_kernel(const int64_t* offs, const uint8_t* bytes,
 
 Tensor minhash(Tensor offsets, Tensor bytes, int64_t num_hashes,
                int64_t ngram_size, Tensor perm_a, Tensor perm_b) {
-  TORCH_CHECK(ngram_size <= 16, "ngram_size <= 16");
-  TORCH_CHECK(num_hashes <= MAX_PERMS_PER_LANE * WAVE,
-              "num_hashes <= 512");
+  TORCH_CHECK(ngram_size >= 1 && ngram_size <= 16,
+              "1 <= ngram_size <= 16");
+  TORCH_CHECK(num_hashes >= 1 && num_hashes <= MAX_PERMS_PER_LANE * WAVE,
+              "1 <= num_hashes <= 512");
+  TORCH_CHECK(perm_a.numel() >= num_hashes && perm_b.numel() >= num_hashes,
+              "perm_a / perm_b shorter than num_hashes");
   auto dev = offsets.device();
   int64_t n = offsets.numel() - 1;
   auto out = torch::empty({n * num_hashes},
@@ -175,6 +178,10 @@ __global__ void image_resize_kernel(const uint8_t* src,
     int ox = (int)((rem / channels) % out_w);
     int c = (int)(rem % channels);
     int ih = src_h[img], iw = src_w[img];
+    if (ih <= 0 || iw <= 0) {  // null / undecodable row: no source bytes
+      out[j] = 0;
+      continue;
+    }
     const uint8_t* s = src + src_off[img];
     float fy = (oy + 0.5f) * ih / out_h - 0.5f;
     float fx = (ox + 0.5f) * iw / out_w - 0.5f;
@@ -196,6 +203,8 @@ __global__ void image_resize_kernel(const uint8_t* src,
 Tensor image_resize(Tensor src_bytes, Tensor src_off, Tensor src_h,
                     Tensor src_w, int64_t channels, int64_t out_h,
                     int64_t out_w) {
+  TORCH_CHECK(channels >= 1 && out_h >= 1 && out_w >= 1,
+              "image_resize: channels, out_h, out_w >= 1");
   auto dev = src_bytes.device();
   int64_t n = src_h.numel();
   auto out = torch::empty({n * out_h * out_w * channels},
@@ -256,6 +265,7 @@ __global__ void simhash_kernel(const int64_t* offs, const uint8_t* bytes,
 }
 
 Tensor simhash(Tensor offsets, Tensor bytes, int64_t ngram_size) {
+  TORCH_CHECK(ngram_size >= 1, "ngram_size >= 1");
   auto dev = offsets.device();
   int64_t n = offsets.numel() - 1;
   auto out = torch::empty({n}, torch::dtype(torch::kInt64).device(dev));

@@ -827,14 +827,16 @@ class Expression:
 
     def minhash(self, num_hashes: int, ngram_size: int = 1,
                 seed: int = 1) -> "Expression":
-        from ..functions.minhash import minhash_series
+        from ..functions.minhash import check_minhash_args, minhash_series
+        check_minhash_args(num_hashes, ngram_size)
         return Expression(ScalarFn(
             "minhash", minhash_series, [self._node],
             DataType.fixed_size_list(DataType.uint32(), num_hashes),
             (num_hashes, ngram_size, seed)))
 
     def simhash(self, ngram_size: int = 4) -> "Expression":
-        from ..functions.minhash import simhash_series
+        from ..functions.minhash import check_simhash_args, simhash_series
+        check_simhash_args(ngram_size)
         return Expression(ScalarFn(
             "simhash", simhash_series, [self._node],
             DataType.uint64(), (ngram_size,)))

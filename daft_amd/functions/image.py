@@ -288,15 +288,38 @@ def encode_series(s: Series, fmt: str = "PNG") -> Series:
 
 
 def resize_series(s: Series, h: int, w: int) -> Series:
-    """Image struct -> FixedShapeImage (HIP bilinear kernel on GPU)."""
+    """Image struct -> FixedShapeImage (HIP bilinear kernel on GPU).
+
+    Bilinear with half-pixel centres: output pixel o samples the source at
+    ((2*o+1)*in - out) / (2*out), neighbours clamped to the image, and the
+    result rounds half up.  Both devices follow this rule.  The source
+    rows must be 3-channel; a null row, or one without pixels, gives zeros
+    and keeps its null."""
     assert s.dtype.kind == TypeKind.IMAGE, f"resize expects Image, got {s.dtype!r}"
+    if int(h) < 1 or int(w) < 1:
+        raise ValueError(f"image.resize: output size must be >= 1x1, got "
+                         f"{h}x{w}")
     data, ch, hh, ww, _m = s.children
     channels = 3  # fixed-shape output mode RGB (round-1)
     n = len(s)
     out_dt = DataType.fixed_shape_image("RGB", h, w)
+    src_h = hh.data.view(torch.int32)
+    src_w = ww.data.view(torch.int32)
+    if s.validity is not None:
+        # whatever lies under a null row is not an image: resize it as 0x0
+        zero = torch.zeros_like(src_h)
+        src_h = torch.where(s.validity, src_h, zero)
+        src_w = torch.where(s.validity, src_w, zero)
+    # the kernel strides the pixels by `channels`: an L or RGBA row would be
+    # read with the wrong stride (and, for L, past its bytes)
+    bad = (ch.data.view(torch.int16) != channels) & (src_h > 0) & (src_w > 0)
+    if n and bool(bad.any()):
+        i = int(bad.nonzero()[0])
+        raise ValueError(
+            f"image.resize: row {i} has {int(ch.data.view(torch.int16)[i])} "
+            f"channel(s); resize takes {channels}-channel (RGB) images only "
+            f"- decode with mode='RGB' first")
     if _is_gpu(s):
-        src_h = hh.data.view(torch.int32)
-        src_w = ww.data.view(torch.int32)
         flat = native_required().image_resize(
             data.data, data.offsets[:-1].contiguous(), src_h.contiguous(),
             src_w.contiguous(), channels, h, w)
@@ -308,15 +331,15 @@ def resize_series(s: Series, h: int, w: int) -> Series:
     out = torch.zeros(n * h * w * channels, dtype=torch.uint8)
     blob = data.data
     for i in range(n):
-        ih = int(hh.data.view(torch.int32)[i])
-        iw = int(ww.data.view(torch.int32)[i])
-        if ih == 0 or iw == 0:
+        ih, iw = int(src_h[i]), int(src_w[i])
+        if ih <= 0 or iw <= 0:
             continue
         arr = blob[offs[i]:offs[i + 1]].reshape(ih, iw, channels)
         t = arr.permute(2, 0, 1).unsqueeze(0).to(torch.float32)
         r = torch.nn.functional.interpolate(
             t, size=(h, w), mode="bilinear", align_corners=False)
-        r8 = r.clamp(0, 255).round().to(torch.uint8).squeeze(0) \
+        # round half up, as the kernel does (torch.round is half-to-even)
+        r8 = (r + 0.5).floor().clamp(0, 255).to(torch.uint8).squeeze(0) \
             .permute(1, 2, 0).contiguous()
         out[i * h * w * channels:(i + 1) * h * w * channels] = r8.reshape(-1)
     child = Series("item", DataType.uint8(), data=out)

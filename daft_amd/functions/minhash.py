@@ -20,8 +20,59 @@ def _perms(num_hashes: int, seed: int):
     return a, b
 
 
+MAX_NUM_HASHES = 512      # csrc/multimodal.hip: 8 permutations per lane
+MAX_NGRAM_WORDS = 16      # csrc/multimodal.hip: ring of word starts
+
+
+def check_minhash_args(num_hashes: int, ngram_size: int) -> None:
+    """Host-side argument check, the same on both devices and before any
+    kernel launch."""
+    if not 1 <= int(num_hashes) <= MAX_NUM_HASHES:
+        raise ValueError(f"minhash: num_hashes must be in 1..{MAX_NUM_HASHES},"
+                         f" got {num_hashes}")
+    if not 1 <= int(ngram_size) <= MAX_NGRAM_WORDS:
+        raise ValueError(f"minhash: ngram_size must be in "
+                         f"1..{MAX_NGRAM_WORDS}, got {ngram_size}")
+
+
+def check_simhash_args(ngram_size: int) -> None:
+    if int(ngram_size) < 1:
+        raise ValueError(f"simhash: ngram_size must be >= 1, got "
+                         f"{ngram_size}")
+
+
+def _word_spans(b: bytes):
+    """(start, end) of every maximal run of bytes other than 0x20."""
+    spans = []
+    i, n = 0, len(b)
+    while i < n:
+        if b[i] == 0x20:
+            i += 1
+            continue
+        j = b.find(b" ", i)
+        if j < 0:
+            j = n
+        spans.append((i, j))
+        i = j
+    return spans
+
+
 def minhash_series(s: Series, num_hashes: int, ngram_size: int,
                    seed: int) -> Series:
+    """MinHash signature of each row's word n-grams.
+
+    Words are maximal runs of bytes other than the space 0x20.  The gram of
+    words j .. j+n-1 is the RAW byte span of the row from the start of word
+    j to the end of word j+n-1, separators as written: "a  b" (two spaces)
+    and "a b" hash differently.  Both devices use this definition (the
+    CPU path used to re-join the words with single spaces).  Each gram hash
+    h = hash_bytes(span) & (2^61-1) goes through the permutations
+    (a_i*h + b_i) mod (2^61-1); the signature keeps the low 32 bits of
+    each minimum.  A row with fewer than n words (or a null row)
+    holds 0xFFFFFFFF throughout."""
+    check_minhash_args(num_hashes, ngram_size)
+    if s.is_dict():
+        s = s.dict_decode()
     a, b = _perms(num_hashes, seed)
     out_dt = DataType.fixed_size_list(DataType.uint32(), num_hashes)
     if _is_gpu(s):
@@ -33,23 +84,21 @@ def minhash_series(s: Series, num_hashes: int, ngram_size: int,
                        data=flat.view(torch.uint32))
         return Series(s.name, out_dt, children=[child],
                       validity=s.validity, length=len(s))
-    # CPU fallback: same algorithm
-    from ..kernels.rowops import _fnv1a_bytes
-    from .. import kernels
+    # CPU fallback: same definition
     vals = s.to_pylist()
     out = np.full((len(vals), num_hashes), 0xFFFFFFFF, dtype=np.uint32)
     for i, v in enumerate(vals):
         if v is None:
             continue
-        words = v.split(" ") if isinstance(v, str) else v.decode().split(" ")
-        words = [w for w in words if w]
-        grams = [" ".join(words[j:j + ngram_size])
-                 for j in range(max(0, len(words) - ngram_size + 1))]
+        raw = v.encode() if isinstance(v, str) else bytes(v)
+        spans = _word_spans(raw)
+        grams = [raw[spans[j][0]:spans[j + ngram_size - 1][1]]
+                 for j in range(max(0, len(spans) - ngram_size + 1))]
         if not grams:
             continue
         mins = np.full(num_hashes, np.iinfo(np.uint64).max, dtype=np.uint64)
         for g in grams:
-            h = np.uint64(_hash_bytes_py(g.encode()) & MERSENNE61)
+            h = np.uint64(_hash_bytes_py(g) & MERSENNE61)
             with np.errstate(over="ignore"):
                 v64 = (_mulmod61_np(a, h) + b)
             v64 = np.where(v64 >= MERSENNE61, v64 - MERSENNE61, v64)
@@ -94,6 +143,9 @@ def simhash_series(s: Series, ngram_size: int) -> Series:
     /root/reference/src/daft-functions/src/simhash.rs:15-42: per-bit
     majority vote over ngram hashes; our hash is csrc/common.h
     hash_bytes_dev).  Rows shorter than ngram_size fingerprint to 0."""
+    check_simhash_args(ngram_size)
+    if s.is_dict():
+        s = s.dict_decode()
     n = len(s)
     if _is_gpu(s):
         out = native_required().simhash(s.offsets, s.data, ngram_size)

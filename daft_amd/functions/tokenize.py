@@ -234,13 +234,17 @@ def bpe_encode_series(s: Series, tok: BPETokenizer) -> Series:
             lists = res.to_pylist()
             for i in over.tolist():
                 v = vals_py[i]
-                lists[i] = None if v is None else \
-                    tok.encode_py(v.encode("utf-8"))
+                lists[i] = None if v is None else tok.encode_py(_raw(v))
             res = Series.from_pylist(s.name, lists,
                                      DataType.list(DataType.int32()))
         return res.to(s.device)
     vals = s.cpu().to_pylist()
-    out = [None if v is None else tok.encode_py(v.encode("utf-8"))
-           for v in vals]
+    out = [None if v is None else tok.encode_py(_raw(v)) for v in vals]
     res = Series.from_pylist(s.name, out, DataType.list(DataType.int32()))
     return res.to(s.device) if s.is_gpu() else res
+
+
+def _raw(v) -> bytes:
+    """The row's bytes: a string column's text as UTF-8, a binary column's
+    value as it is."""
+    return v.encode("utf-8") if isinstance(v, str) else bytes(v)
