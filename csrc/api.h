@@ -142,3 +142,19 @@ Tensor string_compare(Tensor a_off, Tensor a_bytes, Tensor b_off,
 Tensor regex_match(Tensor offsets, Tensor bytes, Tensor table,
                    Tensor byte_class, Tensor flags, int64_t n_classes,
                    int64_t start);
+// match positions with `re.finditer` semantics (regex_dfa.py SpanProgram):
+// a forward priority DFA finds each match end, a reverse DFA its start; flags
+// are 1 (match) and 4 (dead).  regex_count: matches per row, 0 where `valid`
+// is false, at most `limit` (-1: all).  regex_spans: {starts, ends}, absolute
+// positions in `bytes`, row i's k-th match at match_offsets[i] + k.
+Tensor regex_count(Tensor offsets, Tensor bytes, OptTensor valid,
+                   Tensor fwd_table, Tensor byte_class, Tensor fwd_flags,
+                   int64_t n_classes, int64_t start, int64_t limit);
+std::vector<Tensor> regex_spans(Tensor offsets, Tensor bytes, OptTensor valid,
+                                Tensor fwd_table, Tensor byte_class,
+                                Tensor fwd_flags, int64_t n_classes,
+                                int64_t start, Tensor rev_table,
+                                Tensor rev_flags, int64_t rev_start,
+                                Tensor match_offsets, int64_t limit);
+// out[out_offsets[j] + t] = src[seg_start[j] + t]: uint8 [out_offsets[k]]
+Tensor copy_segments(Tensor src, Tensor seg_start, Tensor out_offsets);

@@ -43,6 +43,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("string_compare", &string_compare, "lexicographic compare");
   m.def("regex_match", &regex_match,
         "boolean regex / LIKE match by DFA tables staged in LDS");
+  m.def("regex_count", &regex_count,
+        "regex matches per row by a forward priority DFA staged in LDS");
+  m.def("regex_spans", &regex_spans,
+        "regex match spans: forward DFA for the end, reverse for the start");
+  m.def("copy_segments", &copy_segments,
+        "ragged byte copy, one thread per output byte");
   m.def("levenshtein", &levenshtein,
         "ASCII Levenshtein distance, one thread per row pair");
   m.def("bpe_encode", &bpe_encode,

@@ -206,53 +206,44 @@ def regexp_match(expr, pattern: str):
     return _e(expr).str.match(pattern)
 
 
+def _span_fn(name, kernel, out_dt, expr, pattern, *args):
+    """A function of the match positions: device columns run the span
+    kernels (kernels/strings.py), the rest one `re` call per row."""
+    _re.compile(pattern)    # a bad pattern fails here, not at evaluation
+
+    def run(s: Series) -> Series:
+        return kernel(s, pattern, *args)
+    return Expression(ScalarFn(name, run, [_to_node(expr)], out_dt))
+
+
 def regexp_count(expr, pattern: str):
-    p = _re.compile(pattern)
-    return _host_map("regexp_count", lambda v: len(p.findall(v)),
-                     DataType.int64())(expr)
+    from ..kernels import strings as k
+    return _span_fn("regexp_count", k.regexp_count, DataType.int64(), expr,
+                    pattern)
 
 
 def regexp_extract(expr, pattern: str, group: int = 0):
-    p = _re.compile(pattern)
-
-    def one(v):
-        m = p.search(v)
-        return m.group(group) if m else None
-    return _host_map("regexp_extract", one)(expr)
+    from ..kernels import strings as k
+    return _span_fn("regexp_extract", k.regexp_extract, DataType.string(),
+                    expr, pattern, group)
 
 
 def regexp_extract_all(expr, pattern: str, group: int = 0):
-    p = _re.compile(pattern)
-
-    def run(s: Series) -> Series:
-        vals = s.cpu().to_pylist()
-        out = [None if v is None else
-               [(m.group(group)) for m in p.finditer(v)] for v in vals]
-        r = Series.from_pylist(s.name, out,
-                               DataType.list(DataType.string()))
-        return r.to(s.device) if s.is_gpu() else r
-    return Expression(ScalarFn("regexp_extract_all", run,
-                               [_to_node(expr)],
-                               DataType.list(DataType.string())))
+    from ..kernels import strings as k
+    return _span_fn("regexp_extract_all", k.regexp_extract_all,
+                    DataType.list(DataType.string()), expr, pattern, group)
 
 
 def regexp_replace(expr, pattern: str, replacement: str):
-    p = _re.compile(pattern)
-    return _host_map("regexp_replace",
-                     lambda v: p.sub(replacement, v))(expr)
+    from ..kernels import strings as k
+    return _span_fn("regexp_replace", k.regexp_replace, DataType.string(),
+                    expr, pattern, replacement)
 
 
 def regexp_split(expr, pattern: str):
-    p = _re.compile(pattern)
-
-    def run(s: Series) -> Series:
-        vals = s.cpu().to_pylist()
-        out = [None if v is None else p.split(v) for v in vals]
-        r = Series.from_pylist(s.name, out,
-                               DataType.list(DataType.string()))
-        return r.to(s.device) if s.is_gpu() else r
-    return Expression(ScalarFn("regexp_split", run, [_to_node(expr)],
-                               DataType.list(DataType.string())))
+    from ..kernels import strings as k
+    return _span_fn("regexp_split", k.regexp_split,
+                    DataType.list(DataType.string()), expr, pattern)
 
 
 # -- distances / phonetics --------------------------------------------------

@@ -13,6 +13,10 @@ not handle explicitly raises `Unsupported` and the caller stays on the host
 `Program.match_host` walks the tables in Python exactly as the kernel does;
 the CPU tests hold it to `re`.
 
+Where the pattern matches (`re.finditer` spans) is a second entry point,
+`compile_spans`, further down: a forward automaton with thread priorities
+and a reverse one, with `SpanProgram.spans_host` as the kernels' walk.
+
 Columns hold valid UTF-8, so one code point is an ASCII byte or a lead byte
 followed by its 1-3 continuation bytes."""
 from __future__ import annotations
@@ -146,7 +150,7 @@ class Program:
 
 class _Builder:
     def __init__(self, mode: str):
-        assert mode in ("search", "full"), mode
+        assert mode in ("search", "full", "spans"), mode
         self.mode = mode
         self.eps: List[List[int]] = []
         self.beg: List[List[int]] = []   # epsilon only at input position 0
@@ -265,6 +269,9 @@ class _Builder:
             if add & _I:
                 self.needs_ascii = True
             return self.seq(sub, s, (fl | add) & ~dele, False, False)
+        if (op is _c.MAX_REPEAT or op is _c.MIN_REPEAT) and \
+                self.mode == "spans":
+            return self.repeat_ordered(op is _c.MAX_REPEAT, av, s, fl)
         if op is _c.MAX_REPEAT or op is _c.MIN_REPEAT:
             # lazy and greedy agree on whether a match exists
             lo, hi, sub = av
@@ -279,6 +286,8 @@ class _Builder:
                     s = self.seq(sub, s, fl, False, False)
                     self.eps[s].append(out)
             return out
+        if op is _c.AT and self.mode == "spans":
+            raise Unsupported("anchor in span mode")
         if op is _c.AT:
             if av in (_c.AT_BEGINNING, _c.AT_BEGINNING_STRING):
                 if not cb:
@@ -296,6 +305,32 @@ class _Builder:
                     self.edge(s, _NL, m)    # `$` is `\n?` + end of input
                 return self.new()           # nothing follows: unreachable
         raise Unsupported(f"opcode {op}")
+
+    def repeat_ordered(self, greedy: bool, av, s: int, fl: int) -> int:
+        """Span mode: the order of a node's epsilon edges is thread
+        priority.  A greedy repeat tries its body before its exit, a lazy
+        one its exit before its body."""
+        lo, hi, sub = av
+        if _can_be_empty(sub):
+            # sre ends a repeat on an empty iteration; the automaton has no
+            # such rule
+            raise Unsupported("repeat whose body can match the empty string")
+        for _ in range(lo):
+            s = self.seq(sub, s, fl, False, False)
+        out = self.new()
+        if hi == _c.MAXREPEAT:
+            loop = self.new()
+            body = self.new()
+            self.eps[s].append(loop)
+            self.eps[loop] += [body, out] if greedy else [out, body]
+            self.eps[self.seq(sub, body, fl, False, False)].append(loop)
+            return out
+        for _ in range(hi - lo):
+            body = self.new()
+            self.eps[s] += [body, out] if greedy else [out, body]
+            s = self.seq(sub, body, fl, False, False)
+        self.eps[s].append(out)
+        return out
 
     def class_items(self, items, s: int, fl: int) -> int:
         negate = False
@@ -464,7 +499,8 @@ def _encode(code: int) -> bytes:
 # entry points
 # ---------------------------------------------------------------------------
 
-def _build_regex(pattern: str, mode: str, flags: int) -> Program:
+def _parse(pattern: str, flags: int):
+    """(op tree, global flags) as `re` itself reads the pattern."""
     if not isinstance(pattern, str):
         raise Unsupported("bytes pattern")
     try:
@@ -476,6 +512,11 @@ def _build_regex(pattern: str, mode: str, flags: int) -> Program:
     gflags = tree.state.flags
     if gflags & ~(_I | _S | _U):
         raise Unsupported("flag")
+    return tree, gflags
+
+
+def _build_regex(pattern: str, mode: str, flags: int) -> Program:
+    tree, gflags = _parse(pattern, flags)
     b = _Builder(mode)
     if gflags & _I:
         b.needs_ascii = True
@@ -537,12 +578,300 @@ _compile_cached = _cached(_build_regex)
 _like_cached = _cached(_build_like)
 
 
+# ---------------------------------------------------------------------------
+# match spans: where the pattern matches, as `re.finditer` reports it
+# ---------------------------------------------------------------------------
+#
+# Two automata, as in RE2.  The forward one keeps its NFA threads in priority
+# order and finds where the leftmost-first match ends; the reverse one is a
+# plain subset construction over the reversed NFA and finds where that match
+# starts.  Scope (everything else raises `Unsupported`): the pattern cannot
+# match the empty string, no repeat body can match the empty string (sre
+# ends a repeat on an empty iteration, an automaton does not), and no
+# anchors (a conditional accept does not compose with the priority cut).
+
+SPAN_MATCH = 1  # forward: a match ends on entering; reverse: one starts here
+
+
+def _can_be_empty(items) -> bool:
+    """Can this op sequence match the empty string?  Unknown ops raise."""
+    for op, av in items:
+        if op in (_c.LITERAL, _c.NOT_LITERAL, _c.ANY, _c.IN):
+            return False
+        if op is _c.BRANCH:
+            if not any(_can_be_empty(a) for a in av[1]):
+                return False
+        elif op is _c.SUBPATTERN:
+            if len(av) != 4:
+                raise Unsupported("group shape")
+            if not _can_be_empty(av[3]):
+                return False
+        elif op is _c.MAX_REPEAT or op is _c.MIN_REPEAT:
+            if av[0] > 0 and not _can_be_empty(av[2]):
+                return False
+        else:
+            raise Unsupported(f"opcode {op}")
+    return True
+
+
+class SpanProgram:
+    """Forward (priority) and reverse DFA tables over one byte-class map.
+    `fwd_table[s, byte_class[b]]` / `rev_table[...]` is the state after
+    byte `b`; both start in state 0."""
+
+    def __init__(self, fwd_table: np.ndarray, fwd_flags: np.ndarray,
+                 rev_table: np.ndarray, rev_flags: np.ndarray,
+                 byte_class: np.ndarray, needs_ascii: bool, n_groups: int):
+        self.fwd_table = fwd_table    # int16 [n_fwd_states, n_classes]
+        self.fwd_flags = fwd_flags    # uint8: SPAN_MATCH | DEAD
+        self.rev_table = rev_table    # int16 [n_rev_states, n_classes]
+        self.rev_flags = rev_flags    # uint8: SPAN_MATCH | DEAD
+        self.byte_class = byte_class  # uint8 [256], shared
+        self.start = 0
+        self.rev_start = 0
+        self.needs_ascii = needs_ascii
+        self.n_groups = n_groups      # capturing groups in the pattern
+        self._lists = None
+
+    @property
+    def n_classes(self) -> int:
+        return self.fwd_table.shape[1]
+
+    @property
+    def nbytes(self) -> int:
+        return (self.fwd_table.nbytes + self.rev_table.nbytes +
+                self.byte_class.nbytes + self.fwd_flags.nbytes +
+                self.rev_flags.nbytes)
+
+    def _walk(self, data: bytes, limit: int, starts: bool) -> list:
+        """The kernels' walk, in Python: ends, or (start, end) pairs."""
+        if self._lists is None:
+            self._lists = (self.fwd_table.ravel().tolist(),
+                           self.fwd_flags.tolist(),
+                           self.rev_table.ravel().tolist(),
+                           self.rev_flags.tolist(),
+                           self.byte_class.tolist())
+        ft, ff, rt, rf, cls = self._lists
+        nc = self.n_classes
+        out = []
+        p, b = 0, len(data)
+        while p < b and len(out) != limit:
+            s = self.start
+            last = -1
+            for q in range(p, b):
+                s = ft[s * nc + cls[data[q]]]
+                f = ff[s]
+                if f & SPAN_MATCH:
+                    last = q + 1
+                if f & DEAD:
+                    break
+            if last < 0:
+                break
+            if starts:
+                s = self.rev_start
+                first = last
+                for q in range(last - 1, p - 1, -1):
+                    s = rt[s * nc + cls[data[q]]]
+                    f = rf[s]
+                    if f & SPAN_MATCH:
+                        first = q
+                    if f & DEAD:
+                        break
+                out.append((first, last))
+            else:
+                out.append(last)
+            p = last
+        return out
+
+    def spans_host(self, data: bytes, limit: int = -1) -> list:
+        """Byte spans of the first `limit` matches (all when -1)."""
+        return self._walk(data, limit, True)
+
+    def count_host(self, data: bytes, limit: int = -1) -> int:
+        return len(self._walk(data, limit, False))
+
+
+def _build_spans(pattern: str, flags: int) -> SpanProgram:
+    tree, gflags = _parse(pattern, flags)
+    if _can_be_empty(tree):
+        raise Unsupported("pattern can match the empty string")
+    b = _Builder("spans")
+    if gflags & _I:
+        b.needs_ascii = True
+    first = b.new()
+    fin = b.new()
+    b.eps[b.seq(tree, first, gflags & (_I | _S), False, False)].append(fin)
+    n = len(b.eps)
+    if any(b.beg[x] or (b.eps[x] and b.edges[x]) for x in range(n)) or \
+            b.eps[fin] or b.edges[fin] or b.end_acc:
+        raise Unsupported("NFA shape")      # priority would be ambiguous
+
+    masks = sorted({m for es in b.edges for m, _ in es})
+    sig: Dict[tuple, int] = {}
+    byte_class = np.zeros(256, dtype=np.uint8)
+    reps: List[int] = []
+    for byte in range(256):
+        key = tuple((m >> byte) & 1 for m in masks)
+        if key not in sig:
+            sig[key] = len(reps)
+            reps.append(byte)
+        byte_class[byte] = sig[key]
+    ncls = len(reps)
+    mask_classes = {m: [c for c, r in enumerate(reps) if (m >> r) & 1]
+                    for m in masks}
+
+    # -- forward: ordered thread lists ---------------------------------------
+    oclosures: Dict[int, tuple] = {}
+
+    def oclosure(node: int) -> tuple:
+        """Nodes with byte edges (and `fin`) reachable by epsilon moves, in
+        priority order: depth first, a node's epsilon edges in order."""
+        got = oclosures.get(node)
+        if got is None:
+            out, seen, stack = [], set(), [node]
+            while stack:
+                x = stack.pop()
+                if x in seen:
+                    continue
+                seen.add(x)
+                if x == fin or b.edges[x]:
+                    out.append(x)
+                stack.extend(reversed(b.eps[x]))
+            got = oclosures[node] = tuple(out)
+        return got
+
+    omoves: Dict[int, Dict[int, tuple]] = {}
+
+    def omove(node: int) -> Dict[int, tuple]:
+        got = omoves.get(node)
+        if got is None:
+            acc: Dict[int, list] = {}
+            for m, t in b.edges[node]:
+                ct = oclosure(t)
+                for c in mask_classes[m]:
+                    lst = acc.setdefault(c, [])
+                    lst.extend(x for x in ct if x not in lst)
+            got = omoves[node] = {c: tuple(v) for c, v in acc.items()}
+        return got
+
+    restart = oclosure(first)
+    # state: (threads in priority order, a match was seen, one ends here)
+    first_key = (restart, False, False)
+    ids = {first_key: 0}
+    order = [first_key]
+    rows: List[List[int]] = []
+    i = 0
+    while i < len(order):
+        threads, seen_match, _ = order[i]
+        node_moves = [omove(x) for x in threads]
+        row = []
+        for c in range(ncls):
+            nxt: List[int] = []
+            have = set()
+            for mv in node_moves:
+                for x in mv.get(c, ()):
+                    if x not in have:
+                        have.add(x)
+                        nxt.append(x)
+            if not seen_match:
+                # the search is unanchored until its first match: a new
+                # thread starts here, below every running one
+                nxt.extend(x for x in restart if x not in have)
+            hit = fin in nxt
+            if hit:
+                nxt = nxt[:nxt.index(fin)]  # lower priorities lose
+            key = (tuple(nxt), seen_match or hit, hit)
+            j = ids.get(key)
+            if j is None:
+                if len(order) >= MAX_STATES:
+                    raise Unsupported(f"more than {MAX_STATES} DFA states")
+                j = ids[key] = len(order)
+                order.append(key)
+            row.append(j)
+        rows.append(row)
+        i += 1
+    fwd = np.asarray(rows, dtype=np.int16).reshape(len(order), ncls)
+    fwd_hit = np.array([k[2] for k in order], dtype=bool)
+    fwd_flags = (fwd_hit * SPAN_MATCH + ~_reaches(fwd, fwd_hit) * DEAD) \
+        .astype(np.uint8)
+
+    # -- reverse: subset construction over the reversed NFA ------------------
+    reps_of: List[List[int]] = [[] for _ in range(n)]
+    redges: List[List[Tuple[int, int]]] = [[] for _ in range(n)]
+    for x in range(n):
+        for y in b.eps[x]:
+            reps_of[y].append(x)
+        for m, t in b.edges[x]:
+            redges[t].append((m, x))
+
+    def rclosure(nodes) -> FrozenSet[int]:
+        seen = set(nodes)
+        stack = list(seen)
+        while stack:
+            x = stack.pop()
+            for y in reps_of[x]:
+                if y not in seen:
+                    seen.add(y)
+                    stack.append(y)
+        return frozenset(seen)
+
+    r0 = rclosure([fin])
+    rids = {r0: 0}
+    rorder = [r0]
+    rrows: List[List[int]] = []
+    i = 0
+    while i < len(rorder):
+        acc: List[set] = [set() for _ in range(ncls)]
+        for x in rorder[i]:
+            for m, t in redges[x]:
+                for c in mask_classes[m]:
+                    acc[c].add(t)
+        row = []
+        for c in range(ncls):
+            key = rclosure(acc[c])
+            j = rids.get(key)
+            if j is None:
+                if len(rorder) >= MAX_STATES:
+                    raise Unsupported(f"more than {MAX_STATES} DFA states")
+                j = rids[key] = len(rorder)
+                rorder.append(key)
+            row.append(j)
+        rrows.append(row)
+        i += 1
+    rev = np.asarray(rrows, dtype=np.int16).reshape(len(rorder), ncls)
+    rev_hit = np.array([first in st for st in rorder], dtype=bool)
+    rev_flags = (rev_hit * SPAN_MATCH + ~_reaches(rev, rev_hit) * DEAD) \
+        .astype(np.uint8)
+
+    # bytes that no state of either automaton tells apart share a class
+    cols, inverse = np.unique(np.concatenate([fwd, rev]).T, axis=0,
+                              return_inverse=True)
+    both = np.ascontiguousarray(cols.T)
+    byte_class = inverse.reshape(-1).astype(np.uint8)[byte_class]
+    prog = SpanProgram(np.ascontiguousarray(both[:len(order)]), fwd_flags,
+                       np.ascontiguousarray(both[len(order):]), rev_flags,
+                       byte_class, b.needs_ascii, tree.state.groups - 1)
+    if prog.nbytes > MAX_TABLE_BYTES:
+        raise Unsupported(f"tables need {prog.nbytes} bytes, "
+                          f"limit {MAX_TABLE_BYTES}")
+    return prog
+
+
+_spans_cached = _cached(_build_spans)
+
+
 def compile(pattern: str, mode: str = "search", flags: int = 0) -> Program:
     """DFA for `re.search` (mode "search") or `re.fullmatch` (mode "full")
     of `pattern`; raises `Unsupported`.  Cached on (pattern, mode, flags)."""
     if mode not in ("search", "full"):
         raise ValueError(f"mode must be 'search' or 'full', got {mode!r}")
     return _compile_cached(pattern, mode, int(flags))
+
+
+def compile_spans(pattern: str, flags: int = 0) -> SpanProgram:
+    """Tables that give the `re.finditer` spans of `pattern`; raises
+    `Unsupported` outside the span-mode scope.  Cached on (pattern, flags)."""
+    return _spans_cached(pattern, int(flags))
 
 
 def like_program(pattern: str, ci: bool = False) -> Program:

@@ -219,6 +219,247 @@ def regexp_match(s: Series, pattern: str) -> Series:
     return _host_regex_pred(s, re.compile(pattern), False)
 
 
+# --- regex match positions: count / extract / replace / split ---------------
+#
+# Device columns whose pattern compiles to a span program (regex_dfa.py
+# compile_spans) stay on the device: count matches per row, scan, write the
+# spans, turn them into byte segments with index arithmetic and copy those
+# with one ragged-copy kernel.  Everything else (CPU columns, patterns
+# outside the span scope, ASCII-only programs over non-ASCII data, capture
+# groups, replacement templates) takes the `_host_regexp_*` helper: one `re`
+# call per row.
+
+_LIST_OF_STRING = DataType.list(DataType.string())
+
+
+def _host_rows(s: Series, f, dtype) -> Series:
+    vals = s.cpu().to_pylist()
+    out = [None if v is None else f(v) for v in vals]
+    r = Series.from_pylist(s.name, out, dtype)
+    return r.to(s.device) if s.is_gpu() else r
+
+
+def _host_regexp_count(s: Series, pattern: str) -> Series:
+    p = re.compile(pattern)
+    return _host_rows(s, lambda v: len(p.findall(v)), DataType.int64())
+
+
+def _host_regexp_extract(s: Series, pattern: str, group: int) -> Series:
+    p = re.compile(pattern)
+
+    def one(v):
+        m = p.search(v)
+        return m.group(group) if m else None
+    return _host_rows(s, one, DataType.string())
+
+
+def _host_regexp_extract_all(s: Series, pattern: str, group: int) -> Series:
+    p = re.compile(pattern)
+    return _host_rows(s, lambda v: [m.group(group) for m in p.finditer(v)],
+                      _LIST_OF_STRING)
+
+
+def _host_regexp_replace(s: Series, pattern: str, replacement: str) -> Series:
+    p = re.compile(pattern)
+    return _host_rows(s, lambda v: p.sub(replacement, v), DataType.string())
+
+
+def _host_regexp_split(s: Series, pattern: str) -> Series:
+    p = re.compile(pattern)
+    return _host_rows(s, p.split, _LIST_OF_STRING)
+
+
+@functools.lru_cache(maxsize=64)
+def _span_tables(prog, device: str):
+    return tuple(torch.from_numpy(a).to(device)
+                 for a in (prog.fwd_table, prog.byte_class, prog.fwd_flags,
+                           prog.rev_table, prog.rev_flags))
+
+
+def _span_program(s: Series, pattern: str):
+    """The span program for a device column (for a dictionary column: for
+    its vocab), or None when the call belongs on the host."""
+    if not _is_gpu(s) or not isinstance(pattern, str):
+        return None
+    try:
+        prog = regex_dfa.compile_spans(pattern)
+    except regex_dfa.Unsupported:
+        return None
+    strings = s.children[0] if s.is_dict() else s
+    if prog.needs_ascii and not (pattern.isascii() and _all_ascii(strings)):
+        return None
+    return prog
+
+
+def _device_counts(s: Series, prog, limit: int) -> torch.Tensor:
+    fwd, cls, fflags, _, _ = _span_tables(prog, str(s.device))
+    return native_required().regex_count(
+        s.offsets, s.data, s.validity, fwd, cls, fflags, prog.n_classes,
+        prog.start, limit)
+
+
+def _device_spans(s: Series, prog, limit: int):
+    """(counts [n], match_offsets [n + 1], starts [m], ends [m]); starts and
+    ends are absolute positions in `s.data`."""
+    counts = _device_counts(s, prog, limit)
+    mo = torch.zeros(len(s) + 1, dtype=torch.int64, device=s.device)
+    torch.cumsum(counts, 0, out=mo[1:])
+    fwd, cls, fflags, rev, rflags = _span_tables(prog, str(s.device))
+    starts, ends = native_required().regex_spans(
+        s.offsets, s.data, s.validity, fwd, cls, fflags, prog.n_classes,
+        prog.start, rev, rflags, prog.rev_start, mo, limit)
+    return counts, mo, starts, ends
+
+
+def _copy_strings(src: torch.Tensor, seg_start: torch.Tensor,
+                  seg_len: torch.Tensor):
+    """(offsets [k + 1], bytes) of the segments, copied in order."""
+    off = torch.zeros(seg_len.numel() + 1, dtype=torch.int64,
+                      device=src.device)
+    torch.cumsum(seg_len, 0, out=off[1:])
+    return off, native_required().copy_segments(
+        src, seg_start.contiguous(), off)
+
+
+def _gaps(s: Series, counts, mo, starts, ends):
+    """The text around the matches.  Per match, (row, rank in its row, where
+    the gap before it starts); per row, where the gap after its last match
+    starts."""
+    n, m = len(s), starts.numel()
+    dev = s.device
+    row = torch.repeat_interleave(
+        torch.arange(n, dtype=torch.int64, device=dev), counts,
+        output_size=m)
+    j = torch.arange(m, dtype=torch.int64, device=dev)
+    rank = j - mo[row]
+    ends_p = torch.cat([ends.new_zeros(1), ends])     # ends_p[j] = ends[j-1]
+    before = torch.where(rank == 0, s.offsets[row], ends_p[:-1])
+    tail = torch.where(counts > 0, ends_p[mo[1:]], s.offsets[:-1])
+    return row, rank, before, tail
+
+
+def regexp_count(s: Series, pattern: str) -> Series:
+    """Non-overlapping matches per row (`len(re.findall)`)."""
+    prog = _span_program(s, pattern)
+    if prog is None:
+        return _host_regexp_count(s, pattern)
+    validity = s.validity
+    if s.is_dict():
+        vocab = s.children[0]
+        codes = s.data.to(torch.int64)
+        counts = _device_counts(vocab, prog, -1)[codes]
+        if vocab.validity is not None:
+            vv = vocab.validity[codes]
+            validity = vv if validity is None else (validity & vv)
+    else:
+        counts = _device_counts(s, prog, -1)
+    return Series(s.name, DataType.int64(), data=counts, validity=validity)
+
+
+def regexp_extract(s: Series, pattern: str, group: int = 0) -> Series:
+    """The first match (`re.search(...).group(group)`); null where there is
+    none."""
+    prog = _span_program(s, pattern) if group == 0 else None
+    if prog is None:
+        return _host_regexp_extract(s, pattern, group)
+    if s.is_dict():
+        return _dict_map(s, lambda v: regexp_extract(v, pattern, group))
+    counts, mo, starts, ends = _device_spans(s, prog, 1)
+    hit = counts > 0
+    # at most one match per row: match k belongs to the k-th row that hit
+    seg_start = torch.zeros_like(counts)
+    seg_len = torch.zeros_like(counts)
+    seg_start[hit] = starts
+    seg_len[hit] = ends - starts
+    off, data = _copy_strings(s.data, seg_start, seg_len)
+    return Series(s.name, DataType.string(), data=data, offsets=off,
+                  validity=hit)
+
+
+def regexp_extract_all(s: Series, pattern: str, group: int = 0) -> Series:
+    """Every match of a row as list<string> (`re.finditer`)."""
+    prog = _span_program(s, pattern) if group == 0 else None
+    if prog is None:
+        return _host_regexp_extract_all(s, pattern, group)
+    s = s.dict_decode()
+    counts, mo, starts, ends = _device_spans(s, prog, -1)
+    off, data = _copy_strings(s.data, starts, ends - starts)
+    child = Series("item", DataType.string(), data=data, offsets=off)
+    return Series(s.name, _LIST_OF_STRING, offsets=mo, children=[child],
+                  validity=s.validity)
+
+
+def regexp_replace(s: Series, pattern: str, replacement: str) -> Series:
+    """`re.sub(pattern, replacement, value)`.  A replacement with a backslash
+    is a template to `re`, not a literal: host."""
+    literal = isinstance(replacement, str) and "\\" not in replacement
+    prog = _span_program(s, pattern) if literal else None
+    if prog is None:
+        return _host_regexp_replace(s, pattern, replacement)
+    if s.is_dict():
+        return _dict_map(s, lambda v: regexp_replace(v, pattern, replacement))
+    n = len(s)
+    counts, mo, starts, ends = _device_spans(s, prog, -1)
+    m = starts.numel()
+    row, rank, before, tail = _gaps(s, counts, mo, starts, ends)
+    # row i is gap, replacement, gap, ..., gap: 2 * counts[i] + 1 segments,
+    # the first of them at 2 * mo[i] + i; the replacement's bytes sit
+    # behind the column's in the copy source
+    rep = _bytes_tensor(replacement.encode(), s.device)
+    src = torch.cat([s.data, rep])
+    k = 2 * m + n
+    seg_start = torch.zeros(k, dtype=torch.int64, device=s.device)
+    seg_len = torch.zeros(k, dtype=torch.int64, device=s.device)
+    gap = 2 * torch.arange(m, dtype=torch.int64, device=s.device) + row
+    seg_start[gap] = before
+    seg_len[gap] = starts - before
+    seg_start[gap + 1] = s.data.numel()
+    seg_len[gap + 1] = rep.numel()
+    last = 2 * mo[1:] + torch.arange(n, dtype=torch.int64, device=s.device)
+    tail_len = s.offsets[1:] - tail
+    if s.validity is not None:
+        tail_len = torch.where(s.validity, tail_len,
+                               torch.zeros_like(tail_len))
+    seg_start[last] = tail
+    seg_len[last] = tail_len
+    off, data = _copy_strings(src, seg_start, seg_len)
+    first = torch.cat([last.new_zeros(1), last + 1])
+    return Series(s.name, DataType.string(), data=data,
+                  offsets=off[first].contiguous(), validity=s.validity)
+
+
+def regexp_split(s: Series, pattern: str) -> Series:
+    """`re.split(pattern, value)` as list<string>.  With a capturing group
+    `re.split` puts the groups between the pieces: host."""
+    prog = _span_program(s, pattern)
+    if prog is None or prog.n_groups:
+        return _host_regexp_split(s, pattern)
+    s = s.dict_decode()
+    n = len(s)
+    counts, mo, starts, ends = _device_spans(s, prog, -1)
+    row, rank, before, tail = _gaps(s, counts, mo, starts, ends)
+    # a row is counts[i] + 1 pieces; a null row none
+    pieces = counts + 1
+    if s.validity is not None:
+        pieces = torch.where(s.validity, pieces, torch.zeros_like(pieces))
+    lo = torch.zeros(n + 1, dtype=torch.int64, device=s.device)
+    torch.cumsum(pieces, 0, out=lo[1:])
+    k = int(lo[-1].item())
+    seg_start = torch.zeros(k, dtype=torch.int64, device=s.device)
+    seg_len = torch.zeros(k, dtype=torch.int64, device=s.device)
+    gap = lo[row] + rank
+    seg_start[gap] = before
+    seg_len[gap] = starts - before
+    has = pieces > 0
+    last = lo[1:][has] - 1
+    seg_start[last] = tail[has]
+    seg_len[last] = (s.offsets[1:] - tail)[has]
+    off, data = _copy_strings(s.data, seg_start, seg_len)
+    child = Series("item", DataType.string(), data=data, offsets=off)
+    return Series(s.name, _LIST_OF_STRING, offsets=lo, children=[child],
+                  validity=s.validity)
+
+
 # --- length / manipulation ------------------------------------------------
 
 def length(s: Series) -> Series:

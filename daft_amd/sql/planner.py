@@ -306,6 +306,20 @@ def _bind_func(e: P.FuncCall, binder) -> Expression:
             raise SQLPlanError(
                 "regexp_match() pattern must be a string literal")
         return regexp_match(args[0], pat.value)
+    if name in ("regexp_count", "regexp_extract", "regexp_extract_all",
+                "regexp_replace", "regexp_split"):
+        # pattern, replacement and group are Python values to the free
+        # functions, not expressions
+        from ..expressions.expressions import Literal
+        from .. import functions as F
+        lits = [a._node for a in args[1:]]
+        if not args or not all(isinstance(x, Literal) for x in lits):
+            raise SQLPlanError(
+                f"{name}() takes a column, then literal arguments")
+        try:
+            return getattr(F, name)(args[0], *[x.value for x in lits])
+        except TypeError as te:
+            raise SQLPlanError(f"bad arguments for {name}(): {te}")
     # fall back to the free-function registry (daft.functions parity
     # surface: sin/levenshtein_distance/to_snake_case/...)
     from .. import functions as F
