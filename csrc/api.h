@@ -135,6 +135,8 @@ std::vector<Tensor> str_concat(const std::vector<Tensor>& offsets,
 Tensor str_char_length(Tensor offsets, Tensor bytes);
 Tensor string_compare(Tensor a_off, Tensor a_bytes, Tensor b_off,
                       Tensor b_bytes);
+// out[out_offsets[j] + t] = src[seg_start[j] + t]: uint8 [out_offsets[k]]
+Tensor copy_segments(Tensor src, Tensor seg_start, Tensor out_offsets);
 
 // regex / LIKE by DFA tables (regex.hip).  table: int16 [n_states,
 // n_classes], byte_class: uint8 [256], flags: uint8 [n_states] (1 matched,
@@ -156,5 +158,3 @@ std::vector<Tensor> regex_spans(Tensor offsets, Tensor bytes, OptTensor valid,
                                 int64_t start, Tensor rev_table,
                                 Tensor rev_flags, int64_t rev_start,
                                 Tensor match_offsets, int64_t limit);
-// out[out_offsets[j] + t] = src[seg_start[j] + t]: uint8 [out_offsets[k]]
-Tensor copy_segments(Tensor src, Tensor seg_start, Tensor out_offsets);

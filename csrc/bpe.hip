@@ -13,9 +13,7 @@
 // built host-side.  Rows longer than BPE_MAX_LEN bytes get count=-1 and
 // fall back to the host tokenizer.
 #include "common.h"
-
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_args.h"
 
 using torch::Tensor;
 
@@ -129,8 +127,16 @@ __global__ void bpe_encode_kernel(const int64_t* __restrict__ offsets,
 
 std::vector<Tensor> bpe_encode(Tensor offsets, Tensor bytes, Tensor byte2id,
                                Tensor table_keys, Tensor table_vals) {
-  int64_t n = offsets.numel() - 1;
-  auto dev = bytes.device();
+  StrCol c = check_strcol("bpe_encode", offsets, bytes);
+  int64_t n = c.n;
+  auto dev = offsets.device();
+  check_tensor("bpe_encode", "byte2id", byte2id, torch::kInt32, dev);
+  check_tensor("bpe_encode", "table_keys", table_keys, torch::kInt64, dev);
+  check_tensor("bpe_encode", "table_vals", table_vals, torch::kInt64, dev);
+  TORCH_CHECK(byte2id.numel() == 256 && table_keys.numel() >= 1 &&
+                  table_keys.numel() == table_vals.numel(),
+              "bpe_encode: byte2id must have 256 entries, and table_keys as "
+              "many as table_vals");
   auto out_ids = torch::zeros({std::max<int64_t>(bytes.numel(), 1)},
                               torch::dtype(torch::kInt32).device(dev));
   auto out_counts = torch::zeros({std::max<int64_t>(n, 1)},
@@ -139,9 +145,7 @@ std::vector<Tensor> bpe_encode(Tensor offsets, Tensor bytes, Tensor byte2id,
   int tsize_mask = (int)table_keys.numel() - 1;
   int grid = (int)std::min<int64_t>(n, 4096);
   hipLaunchKernelGGL(bpe_encode_kernel, dim3(grid), dim3(WAVE), 0,
-                     at::hip::getCurrentHIPStream().stream(),
-                     offsets.data_ptr<int64_t>(),
-                     (const uint8_t*)bytes.data_ptr(),
+                     cur_stream(), c.offs, c.bytes,
                      byte2id.data_ptr<int32_t>(),
                      (const uint64_t*)table_keys.data_ptr<int64_t>(),
                      (const uint64_t*)table_vals.data_ptr<int64_t>(),

@@ -5,9 +5,7 @@
 // and fall back to the host implementation (distance is defined over
 // characters, which equals bytes only for ASCII).
 #include "common.h"
-
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_args.h"
 
 using torch::Tensor;
 
@@ -67,8 +65,10 @@ __global__ void levenshtein_kernel(const int64_t* __restrict__ a_off,
 
 Tensor levenshtein(Tensor a_off, Tensor a_bytes, Tensor b_off,
                    Tensor b_bytes, int64_t max_len) {
-  int64_t n = a_off.numel() - 1;
-  auto dev = a_bytes.device();
+  StrCol a = check_strcol("levenshtein", a_off, a_bytes);
+  auto dev = a_off.device();
+  StrCol b = check_strcol_rows("levenshtein", b_off, b_bytes, a.n, dev);
+  int64_t n = a.n;
   auto out = torch::zeros({std::max<int64_t>(n, 1)},
                           torch::dtype(torch::kInt32).device(dev));
   if (n == 0) return out;
@@ -81,11 +81,7 @@ Tensor levenshtein(Tensor a_off, Tensor a_bytes, Tensor b_off,
   int block = 256;
   int grid = grid_1d(n, block);
   hipLaunchKernelGGL(levenshtein_kernel, dim3(grid), dim3(block), 0,
-                     at::hip::getCurrentHIPStream().stream(),
-                     a_off.data_ptr<int64_t>(),
-                     (const uint8_t*)a_bytes.data_ptr(),
-                     b_off.data_ptr<int64_t>(),
-                     (const uint8_t*)b_bytes.data_ptr(),
+                     cur_stream(), a.offs, a.bytes, b.offs, b.bytes,
                      scratch.data_ptr<int32_t>(), stride, n,
                      (int32_t)max_len, out.data_ptr<int32_t>());
   return out;

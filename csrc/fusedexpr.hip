@@ -15,12 +15,7 @@
 // three-valued logic matching kernels.logical_op.
 #include "common.h"
 
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
-static hipStream_t cur_stream() {
-  return at::hip::getCurrentHIPStream().stream();
-}
+#include "host_args.h"
 
 using torch::Tensor;
 using OptTensor = c10::optional<Tensor>;

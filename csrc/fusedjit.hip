@@ -10,8 +10,7 @@
 // cached kernel is reusable across batches and steps.
 #include "common.h"
 
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_args.h"
 #include <hip/hiprtc.h>
 
 #include <mutex>
@@ -136,7 +135,7 @@ std::vector<Tensor> fused_eval_jit(const std::string& src,
   void* params[] = {&cols_p, &outs_p, &nn};
   int block = 256;
   int grid = grid_1d(n, block, /*items_per_thread=*/2);
-  hipStream_t stream = at::hip::getCurrentHIPStream().stream();
+  hipStream_t stream = cur_stream();
   hipError_t rc = hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0,
                                         stream, params, nullptr);
   if (rc != hipSuccess)

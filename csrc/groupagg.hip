@@ -4,17 +4,12 @@
 // stage per-block partials in LDS (160 KiB/CU) and emit one global atomic
 // per block per live slot; high-cardinality shapes go straight to global
 // atomics (low contention).  Valid-row counters are u32 in LDS, i64 in HBM.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
 
 #include <type_traits>
 
 #include "common.h"
+#include "host_args.h"
 #include "api.h"
-
-static hipStream_t cur_stream() {
-  return at::hip::getCurrentHIPStream().stream();
-}
 
 // ---------------------------------------------------------------------------
 // slot primitives.  f64 min/max slots hold order-encoded bits (unsigned

@@ -8,18 +8,13 @@
 //    count, pass two writes rows with at most one output straight from that
 //    record and resumes the walk there for rows with fan-out.
 // Both probes emit (lidx, ridx) int64 gather maps with lidx ascending.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
 
 #include <limits>
 
 #include "common.h"
+#include "host_args.h"
 #include "row_ops.h"
 #include "api.h"
-
-static hipStream_t cur_stream() {
-  return at::hip::getCurrentHIPStream().stream();
-}
 
 enum JoinMode : int { JOIN_INNER = 0, JOIN_LEFT = 1, JOIN_SEMI = 2,
                       JOIN_ANTI = 3 };

@@ -7,16 +7,10 @@
 //    because all cross-workgroup communication is via atomics
 //  * low-cardinality aggregations stage per-block accumulators in LDS
 //    (160 KiB/CU) and emit one global atomic per block per group
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
 #include "common.h"
+#include "host_args.h"
 #include "row_ops.h"
 #include "api.h"
-
-static hipStream_t cur_stream() {
-  return at::hip::getCurrentHIPStream().stream();
-}
 
 // ---------------------------------------------------------------------------
 // descriptor packing
@@ -215,20 +209,15 @@ struct GatherBytes {  // out row r is source row idx[r]
 };
 
 std::vector<Tensor> take_string(Tensor offsets, Tensor bytes, Tensor idx) {
-  auto dev = offsets.device();
-  int64_t m = idx.numel();
-  auto lens = offsets.slice(0, 1) - offsets.slice(0, 0, offsets.numel() - 1);
-  auto sel_lens = lens.index_select(0, idx);
-  auto out_off = torch::zeros({m + 1}, torch::dtype(torch::kInt64).device(dev));
-  if (m > 0)
-    out_off.slice(0, 1).copy_(torch::cumsum(sel_lens, 0));
-  int64_t total = m > 0 ? out_off[m].item<int64_t>() : 0;
-  auto out = torch::empty({total}, torch::dtype(torch::kUInt8).device(dev));
+  StrCol c = check_strcol("take_string", offsets, bytes);
+  check_tensor("take_string", "idx", idx, torch::kInt64, offsets.device());
+  TORCH_CHECK(idx.dim() == 1, "take_string: idx must be 1-d");
+  auto lens = offsets.slice(0, 1) - offsets.slice(0, 0, c.n);
+  auto [out_off, total] = offsets_from_lens(lens.index_select(0, idx));
+  auto out = torch::empty({total}, bytes.options());
   if (total > 0)
-    launch_out_bytes(out_off, m, total,
-                     GatherBytes{offsets.data_ptr<int64_t>(),
-                                 bytes.data_ptr<uint8_t>(),
-                                 idx.data_ptr<int64_t>(),
+    launch_out_bytes(out_off, idx.numel(), total,
+                     GatherBytes{c.offs, c.bytes, idx.data_ptr<int64_t>(),
                                  out.data_ptr<uint8_t>()});
   return {out_off, out};
 }
@@ -248,17 +237,20 @@ struct MergeStrings {  // out row r is t's row r where m[r], else f's
 
 Tensor merge_strings(Tensor mask, Tensor t_off, Tensor t_bytes, Tensor f_off,
                      Tensor f_bytes, Tensor out_off) {
-  int64_t nrows = mask.numel();
-  int64_t total = nrows > 0 ? out_off[nrows].item<int64_t>() : 0;
-  auto out = torch::empty({total},
-                          torch::dtype(torch::kUInt8).device(mask.device()));
+  StrCol t = check_strcol("merge_strings", t_off, t_bytes);
+  auto dev = t_off.device();
+  StrCol f = check_strcol_rows("merge_strings", f_off, f_bytes, t.n, dev);
+  check_tensor("merge_strings", "mask", mask, torch::kBool, dev);
+  TORCH_CHECK(mask.numel() == t.n, "merge_strings: mask must have ", t.n,
+              " rows");
+  check_tensor("merge_strings", "out_off", out_off, torch::kInt64, dev);
+  TORCH_CHECK(out_off.dim() == 1 && out_off.numel() == t.n + 1,
+              "merge_strings: out_off must have ", t.n + 1, " entries");
+  int64_t total = t.n > 0 ? out_off[t.n].item<int64_t>() : 0;
+  auto out = torch::empty({total}, t_bytes.options());
   if (total > 0)
-    launch_out_bytes(out_off, nrows, total,
-                     MergeStrings{mask.data_ptr<bool>(),
-                                  t_off.data_ptr<int64_t>(),
-                                  t_bytes.data_ptr<uint8_t>(),
-                                  f_off.data_ptr<int64_t>(),
-                                  f_bytes.data_ptr<uint8_t>(),
+    launch_out_bytes(out_off, t.n, total,
+                     MergeStrings{mask.data_ptr<bool>(), t.offs, t.bytes, f.offs, f.bytes,
                                   out.data_ptr<uint8_t>()});
   return out;
 }

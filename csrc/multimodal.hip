@@ -2,15 +2,9 @@
 // bilinear image resize.  Ref capabilities: daft-minhash (portable_simd
 // minhash, src/lib.rs:279-330), hyperloglog (2^14 dense registers), and
 // daft-image resize (src/series.rs:123).
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
 #include "common.h"
+#include "host_args.h"
 #include "api.h"
-
-static hipStream_t mm_stream() {
-  return at::hip::getCurrentHIPStream().stream();
-}
 
 // ---------------------------------------------------------------------------
 // MinHash: one wave per row.  Every lane scans the row's word n-grams
@@ -92,8 +86,11 @@ Tensor minhash(Tensor offsets, Tensor bytes, int64_t num_hashes,
               "1 <= num_hashes <= 512");
   TORCH_CHECK(perm_a.numel() >= num_hashes && perm_b.numel() >= num_hashes,
               "perm_a / perm_b shorter than num_hashes");
+  StrCol c = check_strcol("minhash", offsets, bytes);
   auto dev = offsets.device();
-  int64_t n = offsets.numel() - 1;
+  check_tensor("minhash", "perm_a", perm_a, torch::kInt64, dev);
+  check_tensor("minhash", "perm_b", perm_b, torch::kInt64, dev);
+  int64_t n = c.n;
   auto out = torch::empty({n * num_hashes},
                           torch::dtype(torch::kInt32).device(dev));
   if (n > 0) {
@@ -101,9 +98,8 @@ Tensor minhash(Tensor offsets, Tensor bytes, int64_t num_hashes,
     int waves_per_block = block / WAVE;
     int grid = (int)std::min<int64_t>((n + waves_per_block - 1) /
                                       waves_per_block, kMaxBlocks);
-    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
     hipLaunchKernelGGL(minhash_kernel, dim3(grid), dim3(block), 0,
-                       mm_stream(), offsets.data_ptr<int64_t>(), bp, n,
+                       cur_stream(), c.offs, c.bytes, n,
                        (int)num_hashes, (int)ngram_size,
                        (const uint64_t*)perm_a.data_ptr<int64_t>(),
                        (const uint64_t*)perm_b.data_ptr<int64_t>(),
@@ -145,7 +141,7 @@ Tensor hll_update(Tensor hashes, Tensor gids, Tensor valid,
   if (n > 0) {
     int block = 256;
     hipLaunchKernelGGL(hll_update_kernel, dim3(grid_1d(n, block)),
-                       dim3(block), 0, mm_stream(),
+                       dim3(block), 0, cur_stream(),
                        (const uint64_t*)hashes.data_ptr<int64_t>(),
                        gids.defined() && gids.numel()
                            ? gids.data_ptr<int64_t>() : nullptr,
@@ -213,7 +209,7 @@ Tensor image_resize(Tensor src_bytes, Tensor src_off, Tensor src_h,
     int block = 256;
     int64_t total = out.numel();
     hipLaunchKernelGGL(image_resize_kernel, dim3(grid_1d(total, block)),
-                       dim3(block), 0, mm_stream(),
+                       dim3(block), 0, cur_stream(),
                        src_bytes.data_ptr<uint8_t>(),
                        src_off.data_ptr<int64_t>(),
                        src_h.data_ptr<int32_t>(), src_w.data_ptr<int32_t>(),
@@ -266,17 +262,17 @@ __global__ void simhash_kernel(const int64_t* offs, const uint8_t* bytes,
 
 Tensor simhash(Tensor offsets, Tensor bytes, int64_t ngram_size) {
   TORCH_CHECK(ngram_size >= 1, "ngram_size >= 1");
-  auto dev = offsets.device();
-  int64_t n = offsets.numel() - 1;
-  auto out = torch::empty({n}, torch::dtype(torch::kInt64).device(dev));
+  StrCol c = check_strcol("simhash", offsets, bytes);
+  int64_t n = c.n;
+  auto out = torch::empty(
+      {n}, torch::dtype(torch::kInt64).device(offsets.device()));
   if (n > 0) {
     int block = 256;
     int waves_per_block = block / WAVE;
     int grid = (int)std::min<int64_t>((n + waves_per_block - 1) /
                                       waves_per_block, kMaxBlocks);
-    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
     hipLaunchKernelGGL(simhash_kernel, dim3(grid), dim3(block), 0,
-                       mm_stream(), offsets.data_ptr<int64_t>(), bp, n,
+                       cur_stream(), c.offs, c.bytes, n,
                        (int)ngram_size, (uint64_t*)out.data_ptr<int64_t>());
   }
   return out;

@@ -12,10 +12,8 @@
 //     row count is not capped at 2^31 as it is in the sort.
 // Used by the grace hash join, RepartitionOp and the RCCL exchange through
 // rowops.hash_partition.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
 #include "common.h"
+#include "host_args.h"
 #include "api.h"
 
 constexpr int PART_MAX = 256;
@@ -152,7 +150,7 @@ std::vector<Tensor> hash_partition(Tensor hashes, int64_t num_partitions,
   // a block counts its chunk in int32 LDS cells
   TORCH_CHECK(chunk <= INT32_MAX, "hash_partition: too many rows");
   int nblocks = (int)((n + chunk - 1) / chunk);
-  auto stream = at::hip::getCurrentHIPStream().stream();
+  auto stream = cur_stream();
   const uint64_t* hp = (const uint64_t*)hashes.data_ptr<int64_t>();
 
   auto hist = torch::empty({(int64_t)nblocks, num_partitions}, opts64);

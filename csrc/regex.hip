@@ -2,17 +2,11 @@
 // come from daft_amd/kernels/regex_dfa.py, whose Program.match_host walks
 // them the same way: one lookup per input byte, no backtracking.  Below it,
 // match positions (count / spans) from SpanProgram's forward and reverse
-// tables, and the ragged byte copy that assembles extract / replace / split
-// results from those spans.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
+// tables (strings.hip's copy_segments assembles extract / replace / split
+// results from those spans).
 #include "common.h"
+#include "host_args.h"
 #include "api.h"
-
-static hipStream_t rx_stream() {
-  return at::hip::getCurrentHIPStream().stream();
-}
 
 // state flags, shared with regex_dfa.py
 constexpr uint8_t kRxMatched = 1;  // sticky: True whatever follows
@@ -21,6 +15,22 @@ constexpr uint8_t kRxDead = 4;     // no continuation can match
 
 // the launcher refuses programs whose tables do not fit one block's LDS
 constexpr int64_t kRxMaxLdsBytes = 64 * 1024;
+
+// Every thread of the block copies its share of one automaton into LDS:
+// table, then byte_class (skipped when null), then flags.  The caller's
+// single __syncthreads() follows.
+DEV_INLINE void stage_automaton(int16_t* l_table, const int16_t* table,
+                                int table_len, uint8_t* l_class,
+                                const uint8_t* byte_class, uint8_t* l_flags,
+                                const uint8_t* flags, int n_states) {
+  for (int j = threadIdx.x; j < table_len; j += blockDim.x)
+    l_table[j] = table[j];
+  if (byte_class != nullptr)
+    for (int j = threadIdx.x; j < 256; j += blockDim.x)
+      l_class[j] = byte_class[j];
+  for (int j = threadIdx.x; j < n_states; j += blockDim.x)
+    l_flags[j] = flags[j];
+}
 
 // LDS image: table (int16 [n_states * n_classes]) | byte_class (256) | flags.
 // One thread per row, as str_find_kernel / str_like_kernel: rows are short.
@@ -34,12 +44,8 @@ __global__ void regex_match_kernel(const int64_t* offs, const uint8_t* bytes,
   int16_t* l_table = rx_lds;
   uint8_t* l_class = reinterpret_cast<uint8_t*>(rx_lds + table_len);
   uint8_t* l_flags = l_class + 256;
-  for (int j = threadIdx.x; j < table_len; j += blockDim.x)
-    l_table[j] = table[j];
-  for (int j = threadIdx.x; j < 256; j += blockDim.x)
-    l_class[j] = byte_class[j];
-  for (int j = threadIdx.x; j < n_states; j += blockDim.x)
-    l_flags[j] = flags[j];
+  stage_automaton(l_table, table, table_len, l_class, byte_class, l_flags,
+                  flags, n_states);
   __syncthreads();  // reached by every thread, with or without a row
 
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -88,18 +94,11 @@ __global__ void regex_span_kernel(
   uint8_t* l_class = reinterpret_cast<uint8_t*>(l_rev + rev_len);
   uint8_t* l_fflags = l_class + 256;
   uint8_t* l_rflags = l_fflags + fwd_states;
-  for (int j = threadIdx.x; j < fwd_len; j += blockDim.x)
-    l_fwd[j] = fwd_table[j];
-  for (int j = threadIdx.x; j < 256; j += blockDim.x)
-    l_class[j] = byte_class[j];
-  for (int j = threadIdx.x; j < fwd_states; j += blockDim.x)
-    l_fflags[j] = fwd_flags[j];
-  if (kSpans) {
-    for (int j = threadIdx.x; j < rev_len; j += blockDim.x)
-      l_rev[j] = rev_table[j];
-    for (int j = threadIdx.x; j < rev_states; j += blockDim.x)
-      l_rflags[j] = rev_flags[j];
-  }
+  stage_automaton(l_fwd, fwd_table, fwd_len, l_class, byte_class, l_fflags,
+                  fwd_flags, fwd_states);
+  if (kSpans)
+    stage_automaton(l_rev, rev_table, rev_len, nullptr, nullptr, l_rflags,
+                    rev_flags, rev_states);
   __syncthreads();  // reached by every thread, with or without a row
 
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -151,11 +150,14 @@ __global__ void regex_span_kernel(
 namespace {
 
 struct SpanArgs {
-  int64_t n, fwd_states, rev_states, lds_bytes;
+  StrCol col;
+  const bool* valid;
+  int64_t fwd_states, rev_states, lds_bytes;
 };
 
-// Everything a span launch depends on, checked on the host before any
-// launch.  `rev_table` / `rev_flags` are null for regex_count.
+// Everything a DFA launch depends on, checked on the host before any
+// launch.  `rev_table` / `rev_flags` are null for regex_match and
+// regex_count.
 SpanArgs check_span_program(const char* who, const Tensor& offsets,
                             const Tensor& bytes, const OptTensor& valid,
                             const Tensor& fwd_table, const Tensor& byte_class,
@@ -163,34 +165,15 @@ SpanArgs check_span_program(const char* who, const Tensor& offsets,
                             int64_t start, const Tensor* rev_table,
                             const Tensor* rev_flags, int64_t rev_start,
                             int64_t limit) {
-  TORCH_CHECK(offsets.scalar_type() == torch::kInt64 &&
-                  offsets.is_contiguous() && offsets.dim() == 1 &&
-                  offsets.numel() >= 1,
-              who, ": offsets must be contiguous int64 [n + 1]");
-  TORCH_CHECK(bytes.scalar_type() == torch::kUInt8 && bytes.is_contiguous(),
-              who, ": bytes must be contiguous uint8");
-  TORCH_CHECK(fwd_table.scalar_type() == torch::kInt16 &&
-                  fwd_table.is_contiguous(),
-              who, ": fwd_table must be contiguous int16");
-  TORCH_CHECK(byte_class.scalar_type() == torch::kUInt8 &&
-                  byte_class.is_contiguous() && byte_class.numel() == 256,
-              who, ": byte_class must be contiguous uint8 [256]");
-  TORCH_CHECK(fwd_flags.scalar_type() == torch::kUInt8 &&
-                  fwd_flags.is_contiguous(),
-              who, ": fwd_flags must be contiguous uint8 [n_states]");
-  auto dev = offsets.device();
-  TORCH_CHECK(dev.is_cuda() && bytes.device() == dev &&
-                  fwd_table.device() == dev && byte_class.device() == dev &&
-                  fwd_flags.device() == dev,
-              who, ": all tensors must be on one device");
   SpanArgs r;
-  r.n = offsets.numel() - 1;
-  if (valid.has_value()) {
-    TORCH_CHECK(valid->scalar_type() == torch::kBool &&
-                    valid->is_contiguous() && valid->numel() == r.n &&
-                    valid->device() == dev,
-                who, ": valid must be contiguous bool [n] on the device");
-  }
+  r.col = check_strcol(who, offsets, bytes);
+  auto dev = offsets.device();
+  r.valid = check_valid(who, valid, r.col.n, dev);
+  check_tensor(who, "fwd_table", fwd_table, torch::kInt16, dev);
+  check_tensor(who, "byte_class", byte_class, torch::kUInt8, dev);
+  TORCH_CHECK(byte_class.numel() == 256, who,
+              ": byte_class must have 256 entries");
+  check_tensor(who, "fwd_flags", fwd_flags, torch::kUInt8, dev);
   r.fwd_states = fwd_flags.numel();
   TORCH_CHECK(r.fwd_states >= 1 && n_classes >= 1 && n_classes <= 256,
               who, ": bad program shape");
@@ -204,12 +187,8 @@ SpanArgs check_span_program(const char* who, const Tensor& offsets,
   r.rev_states = 0;
   r.lds_bytes = fwd_table.numel() * 2 + 256 + r.fwd_states;
   if (rev_table != nullptr) {
-    TORCH_CHECK(rev_table->scalar_type() == torch::kInt16 &&
-                    rev_table->is_contiguous() && rev_table->device() == dev,
-                who, ": rev_table must be contiguous int16 on the device");
-    TORCH_CHECK(rev_flags->scalar_type() == torch::kUInt8 &&
-                    rev_flags->is_contiguous() && rev_flags->device() == dev,
-                who, ": rev_flags must be contiguous uint8 on the device");
+    check_tensor(who, "rev_table", *rev_table, torch::kInt16, dev);
+    check_tensor(who, "rev_flags", *rev_flags, torch::kUInt8, dev);
     r.rev_states = rev_flags->numel();
     TORCH_CHECK(r.rev_states >= 1 &&
                     r.rev_states * n_classes == rev_table->numel(),
@@ -226,22 +205,43 @@ SpanArgs check_span_program(const char* who, const Tensor& offsets,
 
 }  // namespace
 
+Tensor regex_match(Tensor offsets, Tensor bytes, Tensor table,
+                   Tensor byte_class, Tensor flags, int64_t n_classes,
+                   int64_t start) {
+  SpanArgs r = check_span_program("regex_match", offsets, bytes, c10::nullopt,
+                                  table, byte_class, flags, n_classes, start,
+                                  nullptr, nullptr, 0, -1);
+  int64_t n = r.col.n;
+  auto out = torch::empty(
+      {n}, torch::dtype(torch::kBool).device(offsets.device()));
+  if (n > 0) {
+    int block = 256;
+    hipLaunchKernelGGL(regex_match_kernel, dim3(grid_1d(n, block)),
+                       dim3(block), (size_t)r.lds_bytes, cur_stream(),
+                       r.col.offs, r.col.bytes, n, table.data_ptr<int16_t>(),
+                       byte_class.data_ptr<uint8_t>(),
+                       flags.data_ptr<uint8_t>(), (int)table.numel(),
+                       (int)r.fwd_states, (int)n_classes, (int)start,
+                       out.data_ptr<bool>());
+  }
+  return out;
+}
+
 Tensor regex_count(Tensor offsets, Tensor bytes, OptTensor valid,
                    Tensor fwd_table, Tensor byte_class, Tensor fwd_flags,
                    int64_t n_classes, int64_t start, int64_t limit) {
   SpanArgs r = check_span_program("regex_count", offsets, bytes, valid,
                                   fwd_table, byte_class, fwd_flags, n_classes,
                                   start, nullptr, nullptr, 0, limit);
+  int64_t n = r.col.n;
   auto out = torch::empty(
-      {r.n}, torch::dtype(torch::kInt64).device(offsets.device()));
-  if (r.n > 0) {
+      {n}, torch::dtype(torch::kInt64).device(offsets.device()));
+  if (n > 0) {
     int block = 256;
-    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
-    const bool* vp = valid.has_value() ? valid->data_ptr<bool>() : nullptr;
     hipLaunchKernelGGL(
-        regex_span_kernel<false>, dim3(grid_1d(r.n, block)), dim3(block),
-        (size_t)r.lds_bytes, rx_stream(), offsets.data_ptr<int64_t>(), bp,
-        (int64_t)bytes.numel(), vp, r.n, fwd_table.data_ptr<int16_t>(),
+        regex_span_kernel<false>, dim3(grid_1d(n, block)), dim3(block),
+        (size_t)r.lds_bytes, cur_stream(), r.col.offs, r.col.bytes,
+        r.col.nbytes, r.valid, n, fwd_table.data_ptr<int16_t>(),
         (const int16_t*)nullptr, byte_class.data_ptr<uint8_t>(),
         fwd_flags.data_ptr<uint8_t>(), (const uint8_t*)nullptr,
         (int)fwd_table.numel(), 0, (int)r.fwd_states, 0, (int)n_classes,
@@ -261,14 +261,13 @@ std::vector<Tensor> regex_spans(Tensor offsets, Tensor bytes, OptTensor valid,
                                   fwd_table, byte_class, fwd_flags, n_classes,
                                   start, &rev_table, &rev_flags, rev_start,
                                   limit);
+  int64_t n = r.col.n;
   auto dev = offsets.device();
-  TORCH_CHECK(match_offsets.scalar_type() == torch::kInt64 &&
-                  match_offsets.is_contiguous() &&
-                  match_offsets.numel() == r.n + 1 &&
-                  match_offsets.device() == dev,
-              "regex_spans: match_offsets must be contiguous int64 [n + 1] "
-              "on the device");
-  int64_t m = match_offsets[r.n].item<int64_t>();
+  check_tensor("regex_spans", "match_offsets", match_offsets, torch::kInt64,
+               dev);
+  TORCH_CHECK(match_offsets.numel() == n + 1,
+              "regex_spans: match_offsets must have n + 1 entries");
+  int64_t m = match_offsets[n].item<int64_t>();
   TORCH_CHECK(m >= 0, "regex_spans: match_offsets must end at the number of "
                       "matches, got ", m);
   auto opts = torch::dtype(torch::kInt64).device(dev);
@@ -276,14 +275,12 @@ std::vector<Tensor> regex_spans(Tensor offsets, Tensor bytes, OptTensor valid,
   // than the row has) reads as the empty span at 0
   auto starts = torch::zeros({m}, opts);
   auto ends = torch::zeros({m}, opts);
-  if (r.n > 0 && m > 0) {
+  if (n > 0 && m > 0) {
     int block = 256;
-    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
-    const bool* vp = valid.has_value() ? valid->data_ptr<bool>() : nullptr;
     hipLaunchKernelGGL(
-        regex_span_kernel<true>, dim3(grid_1d(r.n, block)), dim3(block),
-        (size_t)r.lds_bytes, rx_stream(), offsets.data_ptr<int64_t>(), bp,
-        (int64_t)bytes.numel(), vp, r.n, fwd_table.data_ptr<int16_t>(),
+        regex_span_kernel<true>, dim3(grid_1d(n, block)), dim3(block),
+        (size_t)r.lds_bytes, cur_stream(), r.col.offs, r.col.bytes,
+        r.col.nbytes, r.valid, n, fwd_table.data_ptr<int16_t>(),
         rev_table.data_ptr<int16_t>(), byte_class.data_ptr<uint8_t>(),
         fwd_flags.data_ptr<uint8_t>(), rev_flags.data_ptr<uint8_t>(),
         (int)fwd_table.numel(), (int)rev_table.numel(), (int)r.fwd_states,
@@ -292,103 +289,4 @@ std::vector<Tensor> regex_spans(Tensor offsets, Tensor bytes, OptTensor valid,
         starts.data_ptr<int64_t>(), ends.data_ptr<int64_t>());
   }
   return {starts, ends};
-}
-
-// Ragged byte copy: out[out_offs[j] + t] = src[seg_start[j] + t].  One thread
-// per output byte; it finds its segment by binary search over out_offs (the
-// last j with out_offs[j] <= byte), which steps over empty segments.
-__global__ void copy_segments_kernel(const uint8_t* src, int64_t src_len,
-                                     const int64_t* seg_start,
-                                     const int64_t* out_offs, int64_t k,
-                                     int64_t total, uint8_t* out) {
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
-       t += stride) {
-    int64_t lo = 0, hi = k;  // out_offs[lo] <= t < out_offs[hi]
-    while (hi - lo > 1) {
-      int64_t mid = lo + (hi - lo) / 2;
-      if (out_offs[mid] <= t) lo = mid; else hi = mid;
-    }
-    int64_t at = seg_start[lo] + (t - out_offs[lo]);
-    out[t] = (at >= 0 && at < src_len) ? src[at] : 0;
-  }
-}
-
-Tensor copy_segments(Tensor src, Tensor seg_start, Tensor out_offsets) {
-  TORCH_CHECK(src.scalar_type() == torch::kUInt8 && src.is_contiguous(),
-              "copy_segments: src must be contiguous uint8");
-  TORCH_CHECK(seg_start.scalar_type() == torch::kInt64 &&
-                  seg_start.is_contiguous() && seg_start.dim() == 1,
-              "copy_segments: seg_start must be contiguous int64 [k]");
-  TORCH_CHECK(out_offsets.scalar_type() == torch::kInt64 &&
-                  out_offsets.is_contiguous() && out_offsets.dim() == 1 &&
-                  out_offsets.numel() == seg_start.numel() + 1,
-              "copy_segments: out_offsets must be contiguous int64 [k + 1]");
-  auto dev = src.device();
-  TORCH_CHECK(dev.is_cuda() && seg_start.device() == dev &&
-                  out_offsets.device() == dev,
-              "copy_segments: all tensors must be on one device");
-  int64_t k = seg_start.numel();
-  int64_t total = k ? out_offsets[k].item<int64_t>() : 0;
-  TORCH_CHECK(total >= 0 && (k == 0 || out_offsets[0].item<int64_t>() == 0),
-              "copy_segments: out_offsets must run from 0 to the output size");
-  auto out = torch::empty({total}, torch::dtype(torch::kUInt8).device(dev));
-  if (total > 0) {
-    int block = 256;
-    const uint8_t* sp = src.numel() ? src.data_ptr<uint8_t>() : nullptr;
-    hipLaunchKernelGGL(copy_segments_kernel, dim3(grid_1d(total, block)),
-                       dim3(block), 0, rx_stream(), sp, (int64_t)src.numel(),
-                       seg_start.data_ptr<int64_t>(),
-                       out_offsets.data_ptr<int64_t>(), k, total,
-                       out.data_ptr<uint8_t>());
-  }
-  return out;
-}
-
-Tensor regex_match(Tensor offsets, Tensor bytes, Tensor table,
-                   Tensor byte_class, Tensor flags, int64_t n_classes,
-                   int64_t start) {
-  TORCH_CHECK(offsets.scalar_type() == torch::kInt64 &&
-                  offsets.is_contiguous() && offsets.numel() >= 1,
-              "regex_match: offsets must be contiguous int64 [n + 1]");
-  TORCH_CHECK(bytes.scalar_type() == torch::kUInt8 && bytes.is_contiguous(),
-              "regex_match: bytes must be contiguous uint8");
-  TORCH_CHECK(table.scalar_type() == torch::kInt16 && table.is_contiguous(),
-              "regex_match: table must be contiguous int16");
-  TORCH_CHECK(byte_class.scalar_type() == torch::kUInt8 &&
-                  byte_class.is_contiguous() && byte_class.numel() == 256,
-              "regex_match: byte_class must be contiguous uint8 [256]");
-  TORCH_CHECK(flags.scalar_type() == torch::kUInt8 && flags.is_contiguous(),
-              "regex_match: flags must be contiguous uint8 [n_states]");
-  auto dev = offsets.device();
-  TORCH_CHECK(bytes.device() == dev && table.device() == dev &&
-                  byte_class.device() == dev && flags.device() == dev,
-              "regex_match: all tensors must be on one device");
-  int64_t n_states = flags.numel();
-  TORCH_CHECK(n_states >= 1 && n_classes >= 1 && n_classes <= 256,
-              "regex_match: bad program shape");
-  TORCH_CHECK(n_states * n_classes == table.numel(),
-              "regex_match: table has ", table.numel(), " entries, expected ",
-              n_states, " x ", n_classes);
-  TORCH_CHECK(start >= 0 && start < n_states,
-              "regex_match: start state out of range");
-  int64_t lds_bytes = table.numel() * 2 + 256 + n_states;
-  TORCH_CHECK(lds_bytes <= kRxMaxLdsBytes, "regex_match: program needs ",
-              lds_bytes, " bytes of LDS, limit ", kRxMaxLdsBytes);
-
-  int64_t n = offsets.numel() - 1;
-  auto out = torch::empty({n}, torch::dtype(torch::kBool).device(dev));
-  if (n > 0) {
-    int block = 256;
-    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
-    hipLaunchKernelGGL(regex_match_kernel, dim3(grid_1d(n, block)),
-                       dim3(block), (size_t)lds_bytes, rx_stream(),
-                       offsets.data_ptr<int64_t>(), bp, n,
-                       table.data_ptr<int16_t>(),
-                       byte_class.data_ptr<uint8_t>(),
-                       flags.data_ptr<uint8_t>(), (int)table.numel(),
-                       (int)n_states, (int)n_classes, (int)start,
-                       out.data_ptr<bool>());
-  }
-  return out;
 }

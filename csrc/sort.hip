@@ -8,15 +8,9 @@
 // Multi-key / string ordering is composed at the Python layer by repeated
 // stable passes (kernels/rowops.py argsort_multi), so this kernel only ever
 // sorts u64.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
 #include "common.h"
+#include "host_args.h"
 #include "api.h"
-
-static hipStream_t sort_stream() {
-  return at::hip::getCurrentHIPStream().stream();
-}
 
 constexpr int RADIX = 256;
 constexpr int BLOCK = 256;
@@ -115,7 +109,7 @@ Tensor radix_argsort(Tensor keys) {
   for (int pass = 0; pass < 8; ++pass) {
     int shift = pass * 8;
     hipLaunchKernelGGL(radix_hist_kernel, dim3(nblocks), dim3(BLOCK), 0,
-                       sort_stream(),
+                       cur_stream(),
                        (const uint64_t*)keys_a.data_ptr<int64_t>(), n, chunk,
                        shift, hist.data_ptr<int32_t>());
     auto col_totals = hist.sum(0);  // [RADIX] int64
@@ -128,7 +122,7 @@ Tensor radix_argsort(Tensor keys) {
     auto offsets = (digit_base.unsqueeze(0) + block_excl).to(torch::kInt32)
                        .contiguous();
     hipLaunchKernelGGL(radix_scatter_kernel, dim3(nblocks), dim3(BLOCK), 0,
-                       sort_stream(),
+                       cur_stream(),
                        (const uint64_t*)keys_a.data_ptr<int64_t>(),
                        vals_a.data_ptr<int64_t>(), n, chunk, shift,
                        offsets.data_ptr<int32_t>(),
@@ -159,16 +153,14 @@ __global__ void string_chunk_key_kernel(const int64_t* offs,
 }
 
 Tensor string_chunk_key(Tensor offsets, Tensor bytes, int64_t chunk) {
-  auto dev = offsets.device();
-  int64_t n = offsets.numel() - 1;
-  auto out = torch::zeros({n}, torch::dtype(torch::kInt64).device(dev));
-  if (n > 0) {
+  StrCol c = check_strcol("string_chunk_key", offsets, bytes);
+  auto out = torch::zeros(
+      {c.n}, torch::dtype(torch::kInt64).device(offsets.device()));
+  if (c.n > 0) {
     int block = 256;
-    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
-    hipLaunchKernelGGL(string_chunk_key_kernel, dim3(grid_1d(n, block)),
-                       dim3(block), 0, sort_stream(),
-                       offsets.data_ptr<int64_t>(), bp, n, chunk * 8,
-                       (uint64_t*)out.data_ptr<int64_t>());
+    hipLaunchKernelGGL(string_chunk_key_kernel, dim3(grid_1d(c.n, block)),
+                       dim3(block), 0, cur_stream(), c.offs, c.bytes, c.n,
+                       chunk * 8, (uint64_t*)out.data_ptr<int64_t>());
   }
   return out;
 }

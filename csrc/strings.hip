@@ -2,15 +2,9 @@
 // the reference's daft-functions-utf8 kernels.  One thread per row for
 // predicate/search ops (TPC-H string rows are short); byte-parallel for
 // case mapping.
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-
 #include "common.h"
+#include "host_args.h"
 #include "api.h"
-
-static hipStream_t str_stream() {
-  return at::hip::getCurrentHIPStream().stream();
-}
 
 // mode: 0 = find (first match position, -1 if none)
 //       1 = prefix test (0 or -1)
@@ -54,16 +48,15 @@ __global__ void str_find_kernel(const int64_t* offs, const uint8_t* bytes,
 }
 
 Tensor str_find(Tensor offsets, Tensor bytes, Tensor pattern, int64_t mode) {
+  StrCol c = check_strcol("str_find", offsets, bytes);
   auto dev = offsets.device();
-  int64_t n = offsets.numel() - 1;
-  auto out = torch::empty({n}, torch::dtype(torch::kInt64).device(dev));
-  if (n > 0) {
+  check_tensor("str_find", "pattern", pattern, torch::kUInt8, dev);
+  auto out = torch::empty({c.n}, torch::dtype(torch::kInt64).device(dev));
+  if (c.n > 0) {
     int block = 256;
-    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
-    const uint8_t* pp = pattern.numel() ? pattern.data_ptr<uint8_t>() : nullptr;
-    hipLaunchKernelGGL(str_find_kernel, dim3(grid_1d(n, block)), dim3(block),
-                       0, str_stream(), offsets.data_ptr<int64_t>(), bp, n,
-                       pp, pattern.numel(), (int)mode,
+    hipLaunchKernelGGL(str_find_kernel, dim3(grid_1d(c.n, block)),
+                       dim3(block), 0, cur_stream(), c.offs, c.bytes, c.n,
+                       bytes_ptr(pattern), pattern.numel(), (int)mode,
                        out.data_ptr<int64_t>());
   }
   return out;
@@ -122,17 +115,17 @@ __global__ void str_like_kernel(const int64_t* offs, const uint8_t* bytes,
 
 Tensor str_like(Tensor offsets, Tensor bytes, Tensor needles, Tensor lens,
                 bool anchored_prefix, bool anchored_suffix) {
+  StrCol c = check_strcol("str_like", offsets, bytes);
   auto dev = offsets.device();
-  int64_t n = offsets.numel() - 1;
-  auto out = torch::empty({n}, torch::dtype(torch::kBool).device(dev));
-  if (n > 0) {
+  check_tensor("str_like", "needles", needles, torch::kUInt8, dev);
+  check_tensor("str_like", "lens", lens, torch::kInt64, dev);
+  auto out = torch::empty({c.n}, torch::dtype(torch::kBool).device(dev));
+  if (c.n > 0) {
     int block = 256;
-    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
-    const uint8_t* np = needles.numel() ? needles.data_ptr<uint8_t>() : nullptr;
-    hipLaunchKernelGGL(str_like_kernel, dim3(grid_1d(n, block)), dim3(block),
-                       0, str_stream(), offsets.data_ptr<int64_t>(), bp, n,
-                       np, lens.data_ptr<int64_t>(), (int)lens.numel(),
-                       anchored_prefix, anchored_suffix,
+    hipLaunchKernelGGL(str_like_kernel, dim3(grid_1d(c.n, block)),
+                       dim3(block), 0, cur_stream(), c.offs, c.bytes, c.n,
+                       bytes_ptr(needles), lens.data_ptr<int64_t>(),
+                       (int)lens.numel(), anchored_prefix, anchored_suffix,
                        out.data_ptr<bool>());
   }
   return out;
@@ -155,14 +148,13 @@ __global__ void str_case_kernel(const uint8_t* in, int64_t nbytes, int mode,
 }
 
 Tensor str_case(Tensor offsets, Tensor bytes, int64_t mode) {
+  StrCol c = check_strcol("str_case", offsets, bytes);
   auto out = torch::empty_like(bytes);
-  int64_t nb = bytes.numel();
-  if (nb > 0) {
+  if (c.nbytes > 0) {
     int block = 256;
-    hipLaunchKernelGGL(str_case_kernel, dim3(grid_1d(nb, block)),
-                       dim3(block), 0, str_stream(),
-                       bytes.data_ptr<uint8_t>(), nb, (int)mode,
-                       out.data_ptr<uint8_t>());
+    hipLaunchKernelGGL(str_case_kernel, dim3(grid_1d(c.nbytes, block)),
+                       dim3(block), 0, cur_stream(), c.bytes, c.nbytes,
+                       (int)mode, out.data_ptr<uint8_t>());
   }
   return out;
 }
@@ -211,53 +203,70 @@ __global__ void substr_bounds_kernel(const int64_t* offs,
   }
 }
 
-__global__ void substr_copy_kernel(const int64_t* src_start,
-                                   const uint8_t* src_bytes,
-                                   const int64_t* out_off, int64_t n,
-                                   int64_t total, uint8_t* out) {
+// Ragged byte copy: out[out_offs[j] + t] = src[seg_start[j] + t].  One thread
+// per output byte; it finds its segment by binary search over out_offs (the
+// last j with out_offs[j] <= byte), which steps over empty segments.  A
+// position outside src reads as 0.
+__global__ void copy_segments_kernel(const uint8_t* src, int64_t src_len,
+                                     const int64_t* seg_start,
+                                     const int64_t* out_offs, int64_t k,
+                                     int64_t total, uint8_t* out) {
   int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total;
-       j += stride) {
-    // binary search row
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-      int64_t mid = (lo + hi) >> 1;
-      if (out_off[mid + 1] <= j) lo = mid + 1; else hi = mid;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += stride) {
+    int64_t lo = 0, hi = k;  // out_offs[lo] <= t < out_offs[hi]
+    while (hi - lo > 1) {
+      int64_t mid = lo + (hi - lo) / 2;
+      if (out_offs[mid] <= t) lo = mid; else hi = mid;
     }
-    int64_t within = j - out_off[lo];
-    out[j] = src_bytes[src_start[lo] + within];
+    int64_t at = seg_start[lo] + (t - out_offs[lo]);
+    out[t] = (at >= 0 && at < src_len) ? src[at] : 0;
   }
+}
+
+Tensor copy_segments(Tensor src, Tensor seg_start, Tensor out_offsets) {
+  StrCol c = check_strcol("copy_segments", out_offsets, src);
+  check_tensor("copy_segments", "seg_start", seg_start, torch::kInt64,
+               src.device());
+  TORCH_CHECK(seg_start.dim() == 1 && seg_start.numel() == c.n,
+              "copy_segments: out_offsets must have one entry more than "
+              "seg_start [k]");
+  int64_t total = c.n ? out_offsets[c.n].item<int64_t>() : 0;
+  TORCH_CHECK(total >= 0 && (c.n == 0 || out_offsets[0].item<int64_t>() == 0),
+              "copy_segments: out_offsets must run from 0 to the output size");
+  auto out = torch::empty({total},
+                          torch::dtype(torch::kUInt8).device(src.device()));
+  if (total > 0) {
+    int block = 256;
+    hipLaunchKernelGGL(copy_segments_kernel, dim3(grid_1d(total, block)),
+                       dim3(block), 0, cur_stream(), c.bytes, c.nbytes,
+                       seg_start.data_ptr<int64_t>(), c.offs, c.n, total,
+                       out.data_ptr<uint8_t>());
+  }
+  return out;
 }
 
 std::vector<Tensor> str_substr(Tensor offsets, Tensor bytes, int64_t start,
                                int64_t length, bool by_char) {
   TORCH_CHECK(start >= 0, "str_substr: start must be >= 0, got ", start);
-  auto dev = offsets.device();
-  int64_t n = offsets.numel() - 1;
-  auto opts64 = torch::dtype(torch::kInt64).device(dev);
-  auto src_start = torch::empty({n}, opts64);
-  auto new_lens = torch::empty({n}, opts64);
-  auto out_off = torch::zeros({n + 1}, opts64);
+  StrCol c = check_strcol("str_substr", offsets, bytes);
+  auto opts64 = torch::dtype(torch::kInt64).device(offsets.device());
+  auto src_start = torch::empty({c.n}, opts64);
+  auto new_lens = torch::empty({c.n}, opts64);
   int block = 256;
-  if (n > 0) {
-    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
-    hipLaunchKernelGGL(substr_bounds_kernel, dim3(grid_1d(n, block)),
-                       dim3(block), 0, str_stream(),
-                       offsets.data_ptr<int64_t>(), bp, n, start, length,
-                       by_char, src_start.data_ptr<int64_t>(),
+  if (c.n > 0)
+    hipLaunchKernelGGL(substr_bounds_kernel, dim3(grid_1d(c.n, block)),
+                       dim3(block), 0, cur_stream(), c.offs, c.bytes, c.n,
+                       start, length, by_char, src_start.data_ptr<int64_t>(),
                        new_lens.data_ptr<int64_t>());
-    out_off.slice(0, 1).copy_(torch::cumsum(new_lens, 0));
-  }
-  int64_t total = n > 0 ? out_off[n].item<int64_t>() : 0;
-  auto out = torch::empty({total}, torch::dtype(torch::kUInt8).device(dev));
-  if (total > 0) {
-    hipLaunchKernelGGL(substr_copy_kernel, dim3(grid_1d(total, block)),
-                       dim3(block), 0, str_stream(),
+  auto [out_off, total] = offsets_from_lens(new_lens);
+  auto out = torch::empty({total}, bytes.options());
+  if (total > 0)
+    hipLaunchKernelGGL(copy_segments_kernel, dim3(grid_1d(total, block)),
+                       dim3(block), 0, cur_stream(), c.bytes, c.nbytes,
                        src_start.data_ptr<int64_t>(),
-                       bytes.data_ptr<uint8_t>(),
-                       out_off.data_ptr<int64_t>(), n, total,
+                       out_off.data_ptr<int64_t>(), c.n, total,
                        out.data_ptr<uint8_t>());
-  }
   return {out_off, out};
 }
 
@@ -280,30 +289,31 @@ __global__ void str_concat_kernel(const int64_t* const* offs,
 
 std::vector<Tensor> str_concat(const std::vector<Tensor>& offsets,
                                const std::vector<Tensor>& bytes) {
-  auto dev = offsets[0].device();
-  int64_t n = offsets[0].numel() - 1;
+  TORCH_CHECK(!offsets.empty() && offsets.size() == bytes.size(),
+              "str_concat: needs at least one column, and as many offsets "
+              "as bytes tensors");
   int k = (int)offsets.size();
+  StrCol first = check_strcol("str_concat", offsets[0], bytes[0]);
+  auto dev = offsets[0].device();
+  int64_t n = first.n;
+  // column pointers, staged on the host and copied over only if launched
+  auto hoffs = torch::empty({k}, torch::dtype(torch::kInt64));
+  auto hdata = torch::empty({k}, torch::dtype(torch::kInt64));
   auto lens = torch::zeros({n}, torch::dtype(torch::kInt64).device(dev));
-  for (int c = 0; c < k; ++c)
+  for (int c = 0; c < k; ++c) {
+    StrCol col = check_strcol_rows("str_concat", offsets[c], bytes[c], n, dev);
+    hoffs[c] = (int64_t)col.offs;
+    hdata[c] = (int64_t)col.bytes;
     lens += offsets[c].slice(0, 1) - offsets[c].slice(0, 0, n);
-  auto out_off = torch::zeros({n + 1}, torch::dtype(torch::kInt64).device(dev));
-  if (n > 0) out_off.slice(0, 1).copy_(torch::cumsum(lens, 0));
-  int64_t total = n > 0 ? out_off[n].item<int64_t>() : 0;
+  }
+  auto [out_off, total] = offsets_from_lens(lens);
   auto out = torch::empty({total}, torch::dtype(torch::kUInt8).device(dev));
   if (total > 0) {
-    // pointer arrays on device
-    auto hoffs = torch::empty({k}, torch::dtype(torch::kInt64));
-    auto hdata = torch::empty({k}, torch::dtype(torch::kInt64));
-    for (int c = 0; c < k; ++c) {
-      hoffs[c] = (int64_t)offsets[c].data_ptr<int64_t>();
-      hdata[c] = (int64_t)(bytes[c].numel() ? bytes[c].data_ptr<uint8_t>()
-                                            : nullptr);
-    }
     auto doffs = hoffs.to(dev);
     auto ddata = hdata.to(dev);
     int block = 256;
     hipLaunchKernelGGL(str_concat_kernel, dim3(grid_1d(n, block)),
-                       dim3(block), 0, str_stream(),
+                       dim3(block), 0, cur_stream(),
                        (const int64_t* const*)doffs.data_ptr<int64_t>(),
                        (const uint8_t* const*)ddata.data_ptr<int64_t>(), k,
                        out_off.data_ptr<int64_t>(), n,
@@ -325,15 +335,13 @@ __global__ void char_length_kernel(const int64_t* offs, const uint8_t* bytes,
 }
 
 Tensor str_char_length(Tensor offsets, Tensor bytes) {
-  auto dev = offsets.device();
-  int64_t n = offsets.numel() - 1;
-  auto out = torch::zeros({n}, torch::dtype(torch::kInt64).device(dev));
-  if (n > 0) {
+  StrCol c = check_strcol("str_char_length", offsets, bytes);
+  auto out = torch::zeros(
+      {c.n}, torch::dtype(torch::kInt64).device(offsets.device()));
+  if (c.n > 0) {
     int block = 256;
-    const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
-    hipLaunchKernelGGL(char_length_kernel, dim3(grid_1d(n, block)),
-                       dim3(block), 0, str_stream(),
-                       offsets.data_ptr<int64_t>(), bp, n,
+    hipLaunchKernelGGL(char_length_kernel, dim3(grid_1d(c.n, block)),
+                       dim3(block), 0, cur_stream(), c.offs, c.bytes, c.n,
                        out.data_ptr<int64_t>());
   }
   return out;
@@ -361,18 +369,15 @@ __global__ void string_compare_kernel(const int64_t* ao, const uint8_t* ab,
 
 Tensor string_compare(Tensor a_off, Tensor a_bytes, Tensor b_off,
                       Tensor b_bytes) {
+  StrCol a = check_strcol("string_compare", a_off, a_bytes);
   auto dev = a_off.device();
-  int64_t n = a_off.numel() - 1;
-  auto out = torch::zeros({n}, torch::dtype(torch::kInt8).device(dev));
-  if (n > 0) {
+  StrCol b = check_strcol_rows("string_compare", b_off, b_bytes, a.n, dev);
+  auto out = torch::zeros({a.n}, torch::dtype(torch::kInt8).device(dev));
+  if (a.n > 0) {
     int block = 256;
-    const uint8_t* ap = a_bytes.numel() ? a_bytes.data_ptr<uint8_t>() : nullptr;
-    const uint8_t* bp = b_bytes.numel() ? b_bytes.data_ptr<uint8_t>() : nullptr;
-    hipLaunchKernelGGL(string_compare_kernel, dim3(grid_1d(n, block)),
-                       dim3(block), 0, str_stream(),
-                       a_off.data_ptr<int64_t>(), ap,
-                       b_off.data_ptr<int64_t>(), bp, n,
-                       out.data_ptr<int8_t>());
+    hipLaunchKernelGGL(string_compare_kernel, dim3(grid_1d(a.n, block)),
+                       dim3(block), 0, cur_stream(), a.offs, a.bytes, b.offs,
+                       b.bytes, a.n, out.data_ptr<int8_t>());
   }
   return out;
 }

@@ -148,8 +148,10 @@ def take(s: Series, indices: torch.Tensor,
         return Series.make_dict(s.name, s.children[0], codes, validity)
     if k in (TypeKind.STRING, TypeKind.BINARY):
         if _is_gpu(s):
+            # every gather funnels through here, whatever view its index
+            # is; the binding refuses one that is not contiguous
             new_off, new_bytes = native_required().take_string(
-                s.offsets, s.data, safe_idx)
+                s.offsets, s.data, safe_idx.contiguous())
         else:
             new_off, new_bytes = _cpu_take_string(s.offsets, s.data, safe_idx)
         return Series(s.name, s.dtype, data=new_bytes, offsets=new_off,
@@ -916,9 +918,11 @@ def _merge_by_mask(m: torch.Tensor, t: Series, f: Series) -> Series:
         new_off = torch.zeros(n + 1, dtype=torch.int64, device=m.device)
         torch.cumsum(lens, 0, out=new_off[1:])
         if _is_gpu(t):
+            # the condition's data may be an expanded (stride-0) view, which
+            # the binding refuses
             out_bytes = native_required().merge_strings(
-                m, sel_t.offsets, sel_t.data, sel_f.offsets, sel_f.data,
-                new_off)
+                m.contiguous(), sel_t.offsets, sel_t.data, sel_f.offsets,
+                sel_f.data, new_off)
         else:
             out_bytes = _cpu_merge_strings(m, sel_t, sel_f, new_off)
         return Series(t.name, t.dtype, data=out_bytes, offsets=new_off,

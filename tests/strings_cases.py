@@ -331,6 +331,36 @@ def assert_strings(out: Series, expected):
 
 
 # ---------------------------------------------------------------------------
+# string columns that every native entry point refuses on the host
+# ---------------------------------------------------------------------------
+
+REFUSED_VALUES = ["ab", "€", "abc"]       # the 3-row column of these tests
+
+
+def bad_columns(offsets, data) -> list:
+    """(what, offsets, bytes): a valid device column with one thing wrong.
+    None of them reaches a kernel, so none can fault."""
+    return [
+        ("offsets on the CPU", offsets.cpu(), data),
+        ("int32 offsets", offsets.to(torch.int32), data),
+        ("strided offsets", offsets[::2], data),
+        ("offsets without elements", offsets[:0], data),
+        ("int8 bytes", offsets, data.to(torch.int8)),
+        ("bytes on the CPU", offsets, data.cpu()),
+    ]
+
+
+def assert_refuses_bad_columns(binding: str, call, offsets, data):
+    """`call(offsets, bytes)` raises RuntimeError, worded by the binding's
+    own check, for every bad column."""
+    assert not offsets[::2].is_contiguous()
+    for what, o, d in bad_columns(offsets, data):
+        with pytest.raises(RuntimeError, match=binding + ": "):
+            call(o, d)
+            raise AssertionError(f"{binding} accepted {what}")
+
+
+# ---------------------------------------------------------------------------
 # check drivers: the same matrix runs on the CPU path and on the HIP path
 # ---------------------------------------------------------------------------
 

@@ -26,6 +26,7 @@ from daft_amd.kernels import native_required, rowops
 
 import mm_cases as mc
 import rowops_cases as rc
+import strings_cases as sc
 import test_mm_parity as tier
 
 DEV = "cuda:0"
@@ -75,6 +76,46 @@ def test_simhash_row_counts():
 
 def test_simhash_expression():
     tier.check_simhash_expression(DEV)
+
+
+# A bad argument raises on the host, before anything is launched; the valid
+# call after each group shows that the context is still sound.
+_ROWS3 = [v.encode() for v in sc.REFUSED_VALUES]
+
+
+def _col3():
+    s = mc.text_series(_ROWS3, DEV, "binary")
+    return s.offsets, s.data
+
+
+def _col4():
+    s = mc.text_series(_ROWS3 + [b"d"], DEV, "binary")
+    return s.offsets, s.data
+
+
+def test_simhash_refuses_bad_arguments():
+    nat = native_required()
+    off, data = _col3()
+    sc.assert_refuses_bad_columns(
+        "simhash", lambda o, d: nat.simhash(o, d, 2), off, data)
+    got = nat.simhash(off, data, 2).cpu().numpy().view(np.uint64).tolist()
+    assert got == [mc.simhash_oracle(r, 2) for r in _ROWS3]
+
+
+def test_minhash_refuses_bad_arguments():
+    nat = native_required()
+    off, data = _col3()
+    a, b = mc.minhash_perms(4)
+    pa, pb = (_dev_i64(np.array(p, dtype=np.uint64)) for p in (a, b))
+    sc.assert_refuses_bad_columns(
+        "minhash", lambda o, d: nat.minhash(o, d, 4, 1, pa, pb), off, data)
+    for bad_a, bad_b in ((pa.cpu(), pb), (pa, pb.to(torch.int32)),
+                         (torch.cat([pa, pa])[::2], pb)):
+        with pytest.raises(RuntimeError, match="minhash: "):
+            nat.minhash(off, data, 4, 1, bad_a, bad_b)
+    got = nat.minhash(off, data, 4, 1, pa, pb).cpu().numpy()
+    assert (got.view(np.uint32).reshape(3, 4) ==
+            mc.expected_minhash(_ROWS3, 4, 1)).all()
 
 
 # ---------------------------------------------------------------------------
@@ -209,6 +250,29 @@ def test_bpe_raw_binding_flags_long_rows():
             assert ids[offs[i]:offs[i] + counts[i]] == list(want[i]), i
 
 
+def test_bpe_encode_refuses_bad_arguments():
+    nat = native_required()
+    off, data = _col3()
+    byte2id, keys, vals = mc.bpe_table("aa").tokenizer.tables(off.device)
+    sc.assert_refuses_bad_columns(
+        "bpe_encode", lambda o, d: nat.bpe_encode(o, d, byte2id, keys, vals),
+        off, data)
+    for tables in ((byte2id.cpu(), keys, vals),
+                   (byte2id.to(torch.int64), keys, vals),
+                   (byte2id[:255], keys, vals),
+                   (byte2id, keys.to(torch.int32), vals),
+                   (byte2id, keys, vals.cpu()),
+                   (byte2id, keys, vals[:-1])):
+        with pytest.raises(RuntimeError, match="bpe_encode: "):
+            nat.bpe_encode(off, data, *tables)
+    ids, counts = nat.bpe_encode(off, data, byte2id, keys, vals)
+    ids, counts, offs = ids.cpu().tolist(), counts.cpu().tolist(), \
+        off.cpu().tolist()
+    want = mc.expected_bpe("aa", tuple(_ROWS3))
+    assert [ids[offs[i]:offs[i] + counts[i]] for i in range(3)] == \
+        [list(w) for w in want]
+
+
 # ---------------------------------------------------------------------------
 # Levenshtein
 # ---------------------------------------------------------------------------
@@ -254,6 +318,29 @@ def test_levenshtein_raw_binding_flags_rows_for_the_host():
     got = native_required().levenshtein(sa.offsets, sa.data, sb.offsets,
                                         sb.data, 8)
     assert got.cpu().tolist() == [1, -1, -1, -1, -1]
+
+
+def test_levenshtein_refuses_bad_arguments():
+    nat = native_required()
+    off, data = _col3()
+    off4, data4 = _col4()
+    sc.assert_refuses_bad_columns(
+        "levenshtein", lambda o, d: nat.levenshtein(o, d, off, data, 8), off,
+        data)
+    sc.assert_refuses_bad_columns(
+        "levenshtein", lambda o, d: nat.levenshtein(off, data, o, d, 8), off,
+        data)
+    with pytest.raises(RuntimeError, match="levenshtein: "):
+        nat.levenshtein(off, data, off4, data4, 8)
+    with pytest.raises(RuntimeError, match="levenshtein: "):
+        nat.levenshtein(off4, data4, off, data, 8)
+    other = [b"abd", b"e", b""]
+    sb = mc.text_series(other, DEV, "binary")
+    got = nat.levenshtein(off, data, sb.offsets, sb.data, 8)
+    # -1: the row with a byte >= 0x80 is left to the host
+    assert got.cpu().tolist() == \
+        [mc.levenshtein_oracle(x, y) if x.isascii() else -1
+         for x, y in zip(_ROWS3, other)] == [1, -1, 3]
 
 
 # ---------------------------------------------------------------------------

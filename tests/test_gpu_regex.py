@@ -160,6 +160,30 @@ def test_raw_regex_match_refuses_bad_programs():
              n_classes=2, start=0)
 
 
+def test_raw_regex_match_refuses_bad_columns():
+    """A bad column or a table on the CPU fails on the host, before any
+    launch; the valid call afterwards still gives the oracle's answer."""
+    nat = native_required()
+    vals = sc.REFUSED_VALUES
+    s = _column(vals)
+    prog = rd.compile(r"a.", "search")
+    table, byte_class, flags = [
+        torch.from_numpy(a).to(DEV)
+        for a in (prog.table, prog.byte_class, prog.flags)]
+
+    def call(o, d, table=table, byte_class=byte_class, flags=flags):
+        return nat.regex_match(o, d, table, byte_class, flags,
+                               prog.n_classes, prog.start)
+    sc.assert_refuses_bad_columns("regex_match", call, s.offsets, s.data)
+    for bad in (dict(table=table.cpu()), dict(byte_class=byte_class.cpu()),
+                dict(flags=flags.cpu()),
+                dict(flags=torch.cat([flags, flags])[::2])):
+        with pytest.raises(RuntimeError, match="regex_match: "):
+            call(s.offsets, s.data, **bad)
+    assert call(s.offsets, s.data).cpu().tolist() == \
+        rc.o_search(vals, r"a.") == [True, False, True]
+
+
 # ---------------------------------------------------------------------------
 # wrappers: daft_amd/kernels/strings.py on cuda:0 Series
 # ---------------------------------------------------------------------------

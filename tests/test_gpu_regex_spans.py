@@ -1,5 +1,5 @@
-"""The match-position kernels (csrc/regex.hip: regex_count, regex_spans,
-copy_segments) and the five functions built on them in
+"""The match-position kernels (csrc/regex.hip: regex_count, regex_spans;
+csrc/strings.hip: copy_segments) and the five functions built on them in
 daft_amd/kernels/strings.py, against Python `re` and the host table walk:
 multi-byte UTF-8, adjacent matches, row boundaries, sizes that cross the
 256-thread block edge, sliced, dictionary and null-over-bytes columns, and
@@ -297,6 +297,52 @@ def test_raw_bindings_refuse_bad_programs():
         nat.copy_segments(src, seg, off[:2])
     with pytest.raises(RuntimeError):
         nat.copy_segments(src, seg, off + 1)
+
+
+def test_raw_bindings_refuse_bad_columns():
+    """A bad column fails on the host, before any launch; the valid call
+    after each group still gives the oracle's answer."""
+    nat = native_required()
+    vals = sc.REFUSED_VALUES
+    s = _column(vals)
+    t = _tables(rd.compile_spans(r"a."))
+    want = spc.o_spans(vals, r"a.")
+    assert want == [[(0, 2)], [], [(0, 2)]]
+    mo = torch.tensor([0, 1, 1, 2], dtype=torch.int64, device=DEV)
+
+    def spans(o, d, match_offsets=mo, **kw):
+        g = dict(t, **kw)
+        return nat.regex_spans(o, d, None, g["fwd_table"], g["byte_class"],
+                               g["fwd_flags"], g["n_classes"], g["start"],
+                               g["rev_table"], g["rev_flags"], g["rev_start"],
+                               match_offsets, -1)
+    sc.assert_refuses_bad_columns(
+        "regex_count", lambda o, d: _count(t, o, d), s.offsets, s.data)
+    with pytest.raises(RuntimeError, match="regex_count: "):
+        _count(dict(t, fwd_table=t["fwd_table"].cpu()), s.offsets, s.data)
+    with pytest.raises(RuntimeError, match="regex_count: "):
+        _count(t, s.offsets, s.data,
+               valid=torch.ones(3, dtype=torch.bool))       # on the CPU
+    sc.assert_refuses_bad_columns("regex_spans", spans, s.offsets, s.data)
+    for bad in (dict(rev_flags=t["rev_flags"].cpu()),
+                dict(match_offsets=mo.cpu()),
+                dict(match_offsets=torch.cat([mo, mo])[::2])):
+        with pytest.raises(RuntimeError, match="regex_spans: "):
+            spans(s.offsets, s.data, **bad)
+    assert _spans(t, s.offsets, s.data) == ([len(w) for w in want], want)
+
+    # copy_segments: out_offsets and src are its column
+    seg = torch.tensor([3, 0, 5], dtype=torch.int64, device=DEV)
+    sc.assert_refuses_bad_columns(
+        "copy_segments", lambda o, d: nat.copy_segments(d, seg, o),
+        s.offsets, s.data)
+    for bad in (seg.cpu(), seg[:2], torch.cat([seg, seg])[::2]):
+        with pytest.raises(RuntimeError, match="copy_segments: "):
+            nat.copy_segments(s.data, bad, s.offsets)
+    buf = "".join(vals).encode()
+    lens = [len(v.encode()) for v in vals]
+    assert bytes(nat.copy_segments(s.data, seg, s.offsets).cpu().tolist()) \
+        == b"".join(buf[b:b + n] for b, n in zip(seg.cpu().tolist(), lens))
 
 
 # ---------------------------------------------------------------------------

@@ -5,9 +5,16 @@ Python oracle in strings_cases.py: multi-byte UTF-8, sizes that cross the
 null-over-bytes columns.  All comparisons are exact.
 
 The wrapper tests run the same matrix as test_strings_parity.py on cuda:0;
-the raw-binding tests call the extension directly.  The raw bindings are
-never given a zero-length LIKE needle or a negative start: the wrappers
-filter those out and the kernels do not guard against them."""
+the raw-binding tests call the extension directly.  Every binding checks
+its tensors on the host before it launches anything (csrc/host_args.h): a
+column whose offsets are not contiguous int64 [n + 1] on the GPU or whose
+bytes are not contiguous uint8 on the same device, columns of different
+length, and a pattern, mask or index of the wrong dtype or device raise
+RuntimeError; the refusal tests at the end pin that down.  Values in device
+memory are not checked: the raw bindings are never given a zero-length LIKE
+needle, offsets that decrease or point past the bytes, or an index out of
+range; the wrappers filter those out and the kernels do not guard against
+them.  A negative start is refused by str_substr itself."""
 import random
 
 import numpy as np
@@ -321,3 +328,236 @@ def test_radix_argsort_skips_constant_bytes(byte_positions):
     got = native_required().radix_argsort(t).cpu().numpy()
     assert (got == want).all()
     assert len(np.unique(keys)) < n          # ties: stability is checked
+
+
+# ---------------------------------------------------------------------------
+# refusals: a bad argument raises on the host, before anything is launched;
+# the valid call after each group shows that the context is still sound
+# ---------------------------------------------------------------------------
+
+def _col3():
+    s = Series.from_pylist("s", sc.REFUSED_VALUES, DataType.string(),
+                           device=DEV)
+    return s.offsets, s.data
+
+
+def _col4():
+    vals = sc.REFUSED_VALUES + ["d"]
+    s = Series.from_pylist("t", vals, DataType.string(), device=DEV)
+    return s.offsets, s.data, vals
+
+
+def test_str_find_refuses_bad_arguments():
+    nat, vals = native_required(), sc.REFUSED_VALUES
+    off, data = _col3()
+    sc.assert_refuses_bad_columns(
+        "str_find", lambda o, d: nat.str_find(o, d, _pat("b"), 0), off, data)
+    with pytest.raises(RuntimeError, match="str_find: "):
+        nat.str_find(off, data, _pat("b").cpu(), 0)
+    with pytest.raises(RuntimeError, match="str_find: "):
+        nat.str_find(off, data, _pat("abab")[::2], 0)
+    assert nat.str_find(off, data, _pat("b"), 0).cpu().tolist() == \
+        sc.o_find(vals, "b") == [1, -1, 1]
+
+
+def test_str_like_refuses_bad_arguments():
+    nat, vals = native_required(), sc.REFUSED_VALUES
+    off, data = _col3()
+    lens = torch.tensor([1, 1], dtype=torch.int64, device=DEV)
+
+    def call(o, d, blob=_pat("ac"), lens=lens):
+        return nat.str_like(o, d, blob, lens, True, True)
+    sc.assert_refuses_bad_columns("str_like", call, off, data)
+    with pytest.raises(RuntimeError, match="str_like: "):
+        call(off, data, blob=_pat("ac").cpu())
+    with pytest.raises(RuntimeError, match="str_like: "):
+        call(off, data, lens=lens.to(torch.int32))
+    with pytest.raises(RuntimeError, match="str_like: "):
+        call(off, data, lens=lens.cpu())
+    assert call(off, data).cpu().tolist() == sc.o_like(vals, "a%c") == \
+        [False, False, True]
+
+
+def test_str_case_refuses_bad_arguments():
+    nat, vals = native_required(), sc.REFUSED_VALUES
+    off, data = _col3()
+    sc.assert_refuses_bad_columns(
+        "str_case", lambda o, d: nat.str_case(o, d, 1), off, data)
+    assert _strings_of(off, nat.str_case(off, data, 1)) == \
+        [v.encode() for v in sc.o_upper(vals)]
+
+
+def test_str_substr_refuses_bad_arguments():
+    nat, vals = native_required(), sc.REFUSED_VALUES
+    off, data = _col3()
+    sc.assert_refuses_bad_columns(
+        "str_substr", lambda o, d: nat.str_substr(o, d, 1, 1, True), off,
+        data)
+    assert _strings_of(*nat.str_substr(off, data, 1, 1, True)) == \
+        [v.encode() for v in sc.o_substr(vals, 1, 1)] == [b"b", b"", b"b"]
+
+
+def test_str_concat_refuses_bad_arguments():
+    nat, vals = native_required(), sc.REFUSED_VALUES
+    off, data = _col3()
+    off4, data4, _ = _col4()
+    for slot in (0, 1):       # the bad column first, and after a good one
+
+        def call(o, d):
+            offs, datas = [off, off], [data, data]
+            offs[slot], datas[slot] = o, d
+            return nat.str_concat(offs, datas)
+        sc.assert_refuses_bad_columns("str_concat", call, off, data)
+    with pytest.raises(RuntimeError, match="str_concat: "):
+        nat.str_concat([off, off4], [data, data4])
+    with pytest.raises(RuntimeError, match="str_concat: "):
+        nat.str_concat([off4, off], [data4, data])
+    with pytest.raises(RuntimeError, match="str_concat: "):
+        nat.str_concat([], [])
+    with pytest.raises(RuntimeError, match="str_concat: "):
+        nat.str_concat([off, off], [data])
+    assert _strings_of(*nat.str_concat([off, off], [data, data])) == \
+        [v.encode() for v in sc.o_concat(vals, vals)]
+
+
+def test_str_char_length_refuses_bad_arguments():
+    nat, vals = native_required(), sc.REFUSED_VALUES
+    off, data = _col3()
+    sc.assert_refuses_bad_columns("str_char_length", nat.str_char_length,
+                                  off, data)
+    assert nat.str_char_length(off, data).cpu().tolist() == \
+        sc.o_length(vals) == [2, 1, 3]
+
+
+def test_string_compare_refuses_bad_arguments():
+    nat, vals = native_required(), sc.REFUSED_VALUES
+    off, data = _col3()
+    off4, data4, _ = _col4()
+    sc.assert_refuses_bad_columns(
+        "string_compare", lambda o, d: nat.string_compare(o, d, off, data),
+        off, data)
+    sc.assert_refuses_bad_columns(
+        "string_compare", lambda o, d: nat.string_compare(off, data, o, d),
+        off, data)
+    with pytest.raises(RuntimeError, match="string_compare: "):
+        nat.string_compare(off, data, off4, data4)
+    with pytest.raises(RuntimeError, match="string_compare: "):
+        nat.string_compare(off4, data4, off, data)
+    other = ["ab", "a", "abd"]
+    s2 = Series.from_pylist("t", other, DataType.string(), device=DEV)
+    assert nat.string_compare(off, data, s2.offsets, s2.data).cpu() \
+        .tolist() == sc.o_compare3(vals, other) == [0, 1, -1]
+
+
+def test_string_chunk_key_refuses_bad_arguments():
+    nat, vals = native_required(), sc.REFUSED_VALUES
+    off, data = _col3()
+    sc.assert_refuses_bad_columns(
+        "string_chunk_key", lambda o, d: nat.string_chunk_key(o, d, 0), off,
+        data)
+    got = nat.string_chunk_key(off, data, 0).cpu().numpy().view(np.uint64)
+    assert got.tolist() == sc.o_chunk_key(vals, 0)
+
+
+def test_take_string_refuses_bad_arguments():
+    nat = native_required()
+    off, data = _col3()
+    idx = torch.tensor([2, 0, 0, 1], dtype=torch.int64, device=DEV)
+    sc.assert_refuses_bad_columns(
+        "take_string", lambda o, d: nat.take_string(o, d, idx), off, data)
+    for bad in (idx.cpu(), idx.to(torch.int32), idx[::2]):
+        with pytest.raises(RuntimeError, match="take_string: "):
+            nat.take_string(off, data, bad)
+    under = [v.encode() for v in sc.REFUSED_VALUES]
+    assert _strings_of(*nat.take_string(off, data, idx)) == \
+        [under[i] for i in idx.cpu().tolist()]
+
+
+def test_merge_strings_refuses_bad_arguments():
+    nat, t_vals = native_required(), sc.REFUSED_VALUES
+    t_off, t_data = _col3()
+    f_vals = ["xyz", "", "é"]
+    f = Series.from_pylist("f", f_vals, DataType.string(), device=DEV)
+    f_off, f_data = f.offsets, f.data
+    off4, data4, _ = _col4()
+    mask = torch.tensor([True, False, False], device=DEV)
+    want = [(t if m else v).encode()
+            for m, t, v in zip(mask.cpu().tolist(), t_vals, f_vals)]
+    out_off = torch.tensor(np.cumsum([0] + [len(w) for w in want]),
+                           dtype=torch.int64, device=DEV)
+    sc.assert_refuses_bad_columns(
+        "merge_strings",
+        lambda o, d: nat.merge_strings(mask, o, d, f_off, f_data, out_off),
+        t_off, t_data)
+    sc.assert_refuses_bad_columns(
+        "merge_strings",
+        lambda o, d: nat.merge_strings(mask, t_off, t_data, o, d, out_off),
+        f_off, f_data)
+    mask4 = torch.tensor([True, False, False, True], device=DEV)
+    out_off4 = torch.cat([out_off, out_off[-1:]])
+    for args in ((mask, t_off, t_data, off4, data4, out_off),
+                 (mask, off4, data4, f_off, f_data, out_off),
+                 (mask4, t_off, t_data, f_off, f_data, out_off),
+                 (mask, t_off, t_data, f_off, f_data, out_off4),
+                 (mask.cpu(), t_off, t_data, f_off, f_data, out_off),
+                 (mask.to(torch.uint8), t_off, t_data, f_off, f_data,
+                  out_off),
+                 (mask, t_off, t_data, f_off, f_data,
+                  out_off.to(torch.int32)),
+                 (mask, t_off, t_data, f_off, f_data, out_off.cpu())):
+        with pytest.raises(RuntimeError, match="merge_strings: "):
+            nat.merge_strings(*args)
+    out = nat.merge_strings(mask, t_off, t_data, f_off, f_data, out_off)
+    assert _strings_of(out_off, out) == want == [b"ab", b"", "é".encode()]
+
+
+# ---------------------------------------------------------------------------
+# str_substr through the ragged copy it shares with copy_segments, at the
+# shapes where the per-byte search for the output row can go wrong
+# ---------------------------------------------------------------------------
+
+def _substr_rows(name):
+    """(values, start, length) of one shape."""
+    if name == "all_empty":          # total == 0: nothing is launched
+        return ["ab", "", "€", "abcd"], 5, None
+    if name == "empty_runs":
+        # 300 rows: the first 5 and last 5 results are empty (rows shorter
+        # than start), and so are runs of 1, 2, .. rows in between
+        vals, gap, run = [], 0, 1
+        for i in range(290):
+            if gap == 0:
+                vals += [""] * run
+                gap, run = 7, run % 6 + 1
+            else:
+                vals.append("é" * 2 + sc.ALPHABET[i % 11] * (1 + i % 9))
+                gap -= 1
+        vals = ["", "a", "é", "ab", "b"] + vals[:290] + ["é", "", "ab", "a",
+                                                           ""]
+        return vals, 2, 5
+    if name == "one_long_row":       # 600 bytes out: two block edges
+        return ["x" + "ab€" * 120], 1, None
+    assert name == "one_row"
+    return ["a€b"], 1, 1
+
+
+@pytest.mark.parametrize("by_char", [True, False])
+@pytest.mark.parametrize("name", ["all_empty", "empty_runs", "one_long_row",
+                                  "one_row"])
+def test_str_substr_row_search(name, by_char):
+    vals, start, length = _substr_rows(name)
+    s = Series.from_pylist("s", vals, DataType.string(), device=DEV)
+    src = vals if by_char else [v.encode() for v in vals]
+    want = [v.encode() if by_char else v
+            for v in sc.o_substr(src, start, length)]
+    off, data = native_required().str_substr(
+        s.offsets, s.data, start, -1 if length is None else length, by_char)
+    assert _strings_of(off, data) == want
+    sizes = [len(w) for w in want]
+    if name == "all_empty":
+        assert sum(sizes) == 0
+    elif name == "empty_runs":
+        assert len(vals) == 300 and not any(sizes[:5] + sizes[-5:])
+        assert any(sizes[i] == sizes[i + 1] == 0 < sizes[i + 2]
+                   for i in range(5, 290))
+    elif name == "one_long_row":
+        assert sizes == [600]
