@@ -137,6 +137,25 @@ Tensor string_compare(Tensor a_off, Tensor a_bytes, Tensor b_off,
                       Tensor b_bytes);
 // out[out_offsets[j] + t] = src[seg_start[j] + t]: uint8 [out_offsets[k]]
 Tensor copy_segments(Tensor src, Tensor seg_start, Tensor out_offsets);
+// the same copy for launchers that hold checked device pointers: `k`
+// segments, `total` output bytes, nothing launched for total == 0
+void launch_copy_segments(const uint8_t* src, int64_t src_len,
+                          const int64_t* seg_start, const int64_t* out_offs,
+                          int64_t k, int64_t total, uint8_t* out);
+
+// text cleanup (strtransform.hip); each returns {out_offsets, out_bytes}.
+// str_strip trims Python's str.isspace set, mode 0 both sides, 1 left,
+// 2 right.  str_right keeps the last n >= 0 code points.  str_reverse
+// reverses by code point.  str_normalize_ascii also returns non_ascii bool
+// [n]: a row with a byte >= 0x80 is flagged and left empty for the caller, a
+// row where `valid` is false is empty and not flagged; every other row has
+// punctuation dropped, A-Z folded and whitespace runs collapsed as asked.
+std::vector<Tensor> str_strip(Tensor offsets, Tensor bytes, int64_t mode);
+std::vector<Tensor> str_right(Tensor offsets, Tensor bytes, int64_t n);
+std::vector<Tensor> str_reverse(Tensor offsets, Tensor bytes);
+std::vector<Tensor> str_normalize_ascii(Tensor offsets, Tensor bytes,
+                                        OptTensor valid, bool remove_punct,
+                                        bool lowercase, bool white_space);
 
 // regex / LIKE by DFA tables (regex.hip).  table: int16 [n_states,
 // n_classes], byte_class: uint8 [256], flags: uint8 [n_states] (1 matched,

@@ -49,6 +49,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "regex match spans: forward DFA for the end, reverse for the start");
   m.def("copy_segments", &copy_segments,
         "ragged byte copy, one thread per output byte");
+  m.def("str_strip", &str_strip,
+        "trim str.isspace characters: both sides, left or right");
+  m.def("str_right", &str_right, "the last n code points");
+  m.def("str_reverse", &str_reverse, "reverse by code point");
+  m.def("str_normalize_ascii", &str_normalize_ascii,
+        "normalize ASCII rows (one wavefront per row), flag the others");
   m.def("levenshtein", &levenshtein,
         "ASCII Levenshtein distance, one thread per row pair");
   m.def("bpe_encode", &bpe_encode,

@@ -224,6 +224,16 @@ __global__ void copy_segments_kernel(const uint8_t* src, int64_t src_len,
   }
 }
 
+void launch_copy_segments(const uint8_t* src, int64_t src_len,
+                          const int64_t* seg_start, const int64_t* out_offs,
+                          int64_t k, int64_t total, uint8_t* out) {
+  if (total <= 0) return;
+  int block = 256;
+  hipLaunchKernelGGL(copy_segments_kernel, dim3(grid_1d(total, block)),
+                     dim3(block), 0, cur_stream(), src, src_len, seg_start,
+                     out_offs, k, total, out);
+}
+
 Tensor copy_segments(Tensor src, Tensor seg_start, Tensor out_offsets) {
   StrCol c = check_strcol("copy_segments", out_offsets, src);
   check_tensor("copy_segments", "seg_start", seg_start, torch::kInt64,
@@ -236,13 +246,8 @@ Tensor copy_segments(Tensor src, Tensor seg_start, Tensor out_offsets) {
               "copy_segments: out_offsets must run from 0 to the output size");
   auto out = torch::empty({total},
                           torch::dtype(torch::kUInt8).device(src.device()));
-  if (total > 0) {
-    int block = 256;
-    hipLaunchKernelGGL(copy_segments_kernel, dim3(grid_1d(total, block)),
-                       dim3(block), 0, cur_stream(), c.bytes, c.nbytes,
-                       seg_start.data_ptr<int64_t>(), c.offs, c.n, total,
-                       out.data_ptr<uint8_t>());
-  }
+  launch_copy_segments(c.bytes, c.nbytes, seg_start.data_ptr<int64_t>(),
+                       c.offs, c.n, total, out.data_ptr<uint8_t>());
   return out;
 }
 
@@ -261,10 +266,7 @@ std::vector<Tensor> str_substr(Tensor offsets, Tensor bytes, int64_t start,
                        new_lens.data_ptr<int64_t>());
   auto [out_off, total] = offsets_from_lens(new_lens);
   auto out = torch::empty({total}, bytes.options());
-  if (total > 0)
-    hipLaunchKernelGGL(copy_segments_kernel, dim3(grid_1d(total, block)),
-                       dim3(block), 0, cur_stream(), c.bytes, c.nbytes,
-                       src_start.data_ptr<int64_t>(),
+  launch_copy_segments(c.bytes, c.nbytes, src_start.data_ptr<int64_t>(),
                        out_off.data_ptr<int64_t>(), c.n, total,
                        out.data_ptr<uint8_t>());
   return {out_off, out};

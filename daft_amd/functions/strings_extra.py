@@ -84,21 +84,16 @@ to_title_case = _host_map(
 
 def normalize(expr, *, remove_punct: bool = False, lowercase: bool = True,
               nfd_unicode: bool = True, white_space: bool = True):
-    """Text normalization (ref: daft-functions-utf8 normalize)."""
-    import unicodedata
+    """Text normalization (ref: daft-functions-utf8 normalize).  Device
+    columns run the ASCII rows in a HIP kernel (kernels/strings.py
+    normalize); rows with other characters go through Python on the host."""
+    from ..kernels import strings as k
 
-    def one(v):
-        if nfd_unicode:
-            v = unicodedata.normalize("NFD", v)
-            v = "".join(c for c in v if not unicodedata.combining(c))
-        if lowercase:
-            v = v.lower()
-        if remove_punct:
-            v = _re.sub(r"[^\w\s]", "", v)
-        if white_space:
-            v = " ".join(v.split())
-        return v
-    return _host_map("normalize", one)(expr)
+    def run(s: Series) -> Series:
+        return k.normalize(s, remove_punct, lowercase, nfd_unicode,
+                           white_space)
+    return Expression(ScalarFn("normalize", run, [_to_node(expr)],
+                               DataType.string()))
 
 
 # -- formatting -------------------------------------------------------------

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import functools
 import re
+import unicodedata
 from typing import List, Optional
 
 import numpy as np
@@ -554,39 +555,122 @@ def upper(s: Series) -> Series:
     return _map_python(s, str.upper)
 
 
-def lstrip(s: Series) -> Series:
-    d = _dict_map(s, lambda v: lstrip(v))
+def _device_strings(s: Series) -> bool:
+    """A plain STRING column on the device: what the text kernels take."""
+    return _is_gpu(s) and s.dtype.kind == TypeKind.STRING and \
+        s.offsets is not None
+
+
+def _strip(s: Series, mode: int, host) -> Series:
+    """Trim `str.isspace` characters: mode 0 both sides, 1 left, 2 right."""
+    d = _dict_map(s, lambda v: _strip(v, mode, host))
     if d is not None:
         return d
-    return _map_python(s, str.lstrip)
+    if _device_strings(s):
+        off, data = native_required().str_strip(s.offsets, s.data, mode)
+        return Series(s.name, s.dtype, data=data, offsets=off,
+                      validity=s.validity)
+    return _map_python(s, host)
+
+
+def lstrip(s: Series) -> Series:
+    return _strip(s, 1, str.lstrip)
 
 
 def rstrip(s: Series) -> Series:
-    d = _dict_map(s, lambda v: rstrip(v))
-    if d is not None:
-        return d
-    return _map_python(s, str.rstrip)
+    return _strip(s, 2, str.rstrip)
 
 
 def strip(s: Series) -> Series:
-    d = _dict_map(s, lambda v: strip(v))
-    if d is not None:
-        return d
-    return _map_python(s, str.strip)
+    return _strip(s, 0, str.strip)
 
 
 def reverse(s: Series) -> Series:
+    """Reverse by code point (`v[::-1]`)."""
     d = _dict_map(s, lambda v: reverse(v))
     if d is not None:
         return d
+    if _device_strings(s):
+        off, data = native_required().str_reverse(s.offsets, s.data)
+        return Series(s.name, s.dtype, data=data, offsets=off,
+                      validity=s.validity)
     return _map_python(s, lambda v: v[::-1])
 
 
 def capitalize(s: Series) -> Series:
+    """`str.capitalize`.  An all-ASCII device column lower-cases with the
+    byte-parallel kernel and upper-cases each row's first byte; a non-ASCII
+    first character can title-case to another length (`ß` -> `Ss`): host."""
     d = _dict_map(s, lambda v: capitalize(v))
     if d is not None:
         return d
+    if _device_strings(s) and _all_ascii(s):
+        out = native_required().str_case(s.offsets, s.data, 0)
+        first = s.offsets[:-1][s.offsets[1:] > s.offsets[:-1]]
+        c = out[first]
+        out[first] = torch.where((c >= 0x61) & (c <= 0x7A), c - 32, c)
+        return Series(s.name, s.dtype, data=out, offsets=s.offsets,
+                      validity=s.validity)
     return _map_python(s, str.capitalize)
+
+
+# --- normalize --------------------------------------------------------------
+
+def _normalize_value(v: str, remove_punct: bool, lowercase: bool,
+                     nfd_unicode: bool, white_space: bool) -> str:
+    if nfd_unicode:
+        v = unicodedata.normalize("NFD", v)
+        v = "".join(c for c in v if not unicodedata.combining(c))
+    if lowercase:
+        v = v.lower()
+    if remove_punct:
+        v = re.sub(r"[^\w\s]", "", v)
+    if white_space:
+        v = " ".join(v.split())
+    return v
+
+
+def _host_normalize(s: Series, remove_punct: bool, lowercase: bool,
+                    nfd_unicode: bool, white_space: bool) -> Series:
+    """Host path of normalize: one Python call per row."""
+    return _host_rows(
+        s, lambda v: _normalize_value(v, remove_punct, lowercase,
+                                      nfd_unicode, white_space),
+        DataType.string())
+
+
+def normalize(s: Series, remove_punct: bool = False, lowercase: bool = True,
+              nfd_unicode: bool = True, white_space: bool = True) -> Series:
+    """Text normalization: strip combining marks after NFD, lower-case, drop
+    what is neither `\\w` nor `\\s`, collapse whitespace runs, each if asked.
+
+    On a device column the ASCII rows, for which NFD is the identity, run in
+    one HIP kernel; it flags the rows that hold a byte >= 0x80, and only
+    those go to the host and are merged back."""
+    flags = (bool(remove_punct), bool(lowercase), bool(nfd_unicode),
+             bool(white_space))
+    d = _dict_map(s, lambda v: normalize(v, *flags))
+    if d is not None:
+        return d
+    if not _device_strings(s):
+        return _host_normalize(s, *flags)
+    n = len(s)
+    off, data, flagged = native_required().str_normalize_ascii(
+        s.offsets, s.data, s.validity, flags[0], flags[1], flags[3])
+    dev = Series(s.name, s.dtype, data=data, offsets=off, validity=s.validity)
+    if not bool(flagged.any().item()):
+        return dev
+    rows = flagged.nonzero().reshape(-1)
+    fixed = _host_normalize(s.take(rows), *flags)
+    # spread the fixed rows over n rows: their bytes are already in order
+    lens = torch.zeros(n, dtype=torch.int64, device=s.device)
+    lens[rows] = fixed.offsets[1:] - fixed.offsets[:-1]
+    spread_off = torch.zeros(n + 1, dtype=torch.int64, device=s.device)
+    torch.cumsum(lens, 0, out=spread_off[1:])
+    spread = Series(s.name, s.dtype, data=fixed.data, offsets=spread_off)
+    from . import if_else
+    cond = Series(s.name, DataType.bool(), data=flagged)
+    return if_else(cond, spread, dev)
 
 
 def concat_str(parts: List[Series]) -> Series:
@@ -618,6 +702,11 @@ def concat_str(parts: List[Series]) -> Series:
 
 
 def split(s: Series, sep: str) -> Series:
+    """`str.split(sep)` as list<string>.  For a non-empty literal separator
+    that is `re.split(re.escape(sep))`, which device columns run on the span
+    kernels."""
+    if _is_gpu(s) and isinstance(sep, str) and sep:
+        return regexp_split(s, re.escape(sep))
     vals = _pylist_str(s.cpu())
     out = [None if v is None else v.split(sep) for v in vals]
     res = Series.from_pylist(s.name, out, DataType.list(DataType.string()))
@@ -628,7 +717,21 @@ def left(s: Series, n: int) -> Series:
     return substr(s, 0, n)
 
 
+def _is_count(n) -> bool:
+    return type(n) is int and n >= 0
+
+
 def right(s: Series, n: int) -> Series:
+    """The last `n` characters.  A negative `n` is a Python slice from the
+    left (`v[-n:]`): host."""
+    if _is_count(n):
+        d = _dict_map(s, lambda v: right(v, n))
+        if d is not None:
+            return d
+        if _device_strings(s):
+            off, data = native_required().str_right(s.offsets, s.data, n)
+            return Series(s.name, s.dtype, data=data, offsets=off,
+                          validity=s.validity)
     return _map_python(s, lambda v: v[-n:] if n else "")
 
 
@@ -649,13 +752,74 @@ def find(s: Series, pat: str) -> Series:
     return Series(s.name, DataType.int64(), data=out, validity=s.validity)
 
 
+def _row_segments(s: Series, src, seg_start, seg_len, per_row: int) -> Series:
+    """Rows made of `per_row` consecutive byte segments of `src` each."""
+    off, data = _copy_strings(src, seg_start, seg_len)
+    return Series(s.name, s.dtype, data=data,
+                  offsets=off[::per_row].contiguous(), validity=s.validity)
+
+
 def repeat(s: Series, n: int) -> Series:
+    """`v * n`.  A device column copies each row as `n` segments."""
+    if _is_count(n):
+        d = _dict_map(s, lambda v: repeat(v, n))
+        if d is not None:
+            return d
+        if _device_strings(s):
+            k = max(n, 1)
+            lens = (s.offsets[1:] - s.offsets[:-1]) if n else \
+                torch.zeros(len(s), dtype=torch.int64, device=s.device)
+            return _row_segments(s, s.data,
+                                 s.offsets[:-1].repeat_interleave(k),
+                                 lens.repeat_interleave(k), k)
     return _map_python(s, lambda v: v * n)
 
 
+def _pad(s: Series, width: int, fillchar: str, left_side: bool) -> Series:
+    """Device lpad / rpad: the first `width` characters of the row, and
+    `width - length` copies of the fill before or after them.  The fill,
+    repeated `width` times, sits behind the column's bytes in the copy
+    source."""
+    nat = native_required()
+    n = len(s)
+    head_off, _ = nat.str_substr(s.offsets, s.data, 0, width, True)
+    head_len = head_off[1:] - head_off[:-1]
+    chars = torch.clamp(nat.str_char_length(s.offsets, s.data), max=width)
+    fill = fillchar.encode()
+    src = torch.cat([s.data, _bytes_tensor(fill * width, s.device)])
+    pad_start = torch.full((n,), s.data.numel(), dtype=torch.int64,
+                           device=s.device)
+    pad_len = (width - chars) * len(fill)
+    parts = [(pad_start, pad_len), (s.offsets[:-1], head_len)]
+    if not left_side:
+        parts.reverse()
+    return _row_segments(
+        s, src, torch.stack([p[0] for p in parts], 1).reshape(-1),
+        torch.stack([p[1] for p in parts], 1).reshape(-1), 2)
+
+
+def _pad_args(width, fillchar) -> bool:
+    # a negative width cuts characters off the end on the host
+    # (`v.rjust(w)[:w]`), and a fill that is not one character raises there
+    return _is_count(width) and isinstance(fillchar, str) and \
+        len(fillchar) == 1
+
+
 def lpad(s: Series, width: int, fillchar: str = " ") -> Series:
+    if _pad_args(width, fillchar):
+        d = _dict_map(s, lambda v: lpad(v, width, fillchar))
+        if d is not None:
+            return d
+        if _device_strings(s):
+            return _pad(s, width, fillchar, True)
     return _map_python(s, lambda v: v.rjust(width, fillchar)[:width])
 
 
 def rpad(s: Series, width: int, fillchar: str = " ") -> Series:
+    if _pad_args(width, fillchar):
+        d = _dict_map(s, lambda v: rpad(v, width, fillchar))
+        if d is not None:
+            return d
+        if _device_strings(s):
+            return _pad(s, width, fillchar, False)
     return _map_python(s, lambda v: v.ljust(width, fillchar)[:width])

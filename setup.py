@@ -23,6 +23,7 @@ setup(
                 "csrc/sort.hip",
                 "csrc/partition.hip",
                 "csrc/strings.hip",
+                "csrc/strtransform.hip",
                 "csrc/regex.hip",
                 "csrc/multimodal.hip",
                 "csrc/fusedexpr.hip",
