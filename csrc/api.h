@@ -85,6 +85,22 @@ Tensor u64_mod(Tensor hashes, int64_t n_partitions);
 std::vector<Tensor> hash_partition(Tensor hashes, int64_t num_partitions,
                                    bool remix);
 
+// as-of probe (asof.hip).  Keys are order-preserving u64 bit patterns held in
+// int64 (rowops._order_key_u64).  The right side is already filtered to usable
+// rows and stably sorted by (group, key).  Group g owns sorted positions
+// [seg_offsets[g], seg_offsets[g+1]).  right_rows[p] is the original right row
+// at sorted position p.
+// left_gids[i] < 0 means "row i matches nothing".
+// Returns int64 [nl]: matched original right row, or -1.
+// Checked on the host: dtype, contiguity, device, rank, matching lengths,
+// strategy, and that nearest comes with allow_exact.  What lives in device
+// memory stays the Python wrapper's job: gids below seg_offsets.numel() - 1,
+// and monotone offsets from 0 to right_keys.numel().
+Tensor asof_probe(Tensor left_keys, Tensor left_gids, Tensor right_keys,
+                  Tensor right_rows, Tensor seg_offsets,
+                  int64_t strategy /*0 backward, 1 forward, 2 nearest*/,
+                  bool allow_exact, bool float_keys);
+
 // multimodal (multimodal.hip)
 Tensor simhash(Tensor offsets, Tensor bytes, int64_t ngram_size);
 Tensor minhash(Tensor offsets, Tensor bytes, int64_t num_hashes,

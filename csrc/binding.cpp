@@ -30,6 +30,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("u64_mod", &u64_mod, "unsigned modulo for hash partitioning");
   m.def("hash_partition", &hash_partition,
         "stable one-pass hash partition -> (perm, counts)");
+  m.def("asof_probe", &asof_probe,
+        "as-of join probe -> matched right row per left row, or -1");
   m.def("simhash", &simhash);
   m.def("minhash", &minhash, "word-ngram MinHash signatures (wave/row)");
   m.def("hll_update", &hll_update, "HyperLogLog register updates");

@@ -232,20 +232,84 @@ class DataFrame:
             other._builder, list(left_on), list(right_on), how, suffix,
             prefix))
 
-    def join_asof(self, other: "DataFrame", left_on: str, right_on: str,
-                  by: Optional[Sequence[str]] = None,
-                  left_by: Optional[Sequence[str]] = None,
-                  right_by: Optional[Sequence[str]] = None,
+    def join_asof(self, other: "DataFrame", left_on: Optional[str] = None,
+                  right_on: Optional[str] = None,
+                  by: Union[str, Sequence[str], None] = None,
+                  left_by: Union[str, Sequence[str], None] = None,
+                  right_by: Union[str, Sequence[str], None] = None,
                   strategy: str = "backward",
-                  suffix: str = "_right") -> "DataFrame":
-        """Nearest-key (as-of) join: for each left row take the closest
-        right row by `on` (backward = latest <=, forward = earliest >=),
-        optionally within matching `by` keys."""
+                  suffix: str = "_right", *,
+                  on: Optional[str] = None,
+                  prefix: Optional[str] = None) -> "DataFrame":
+        """Point-in-time (as-of) join: each left row takes the one right row
+        whose on-key is closest under `strategy`, among the right rows with
+        equal `by` keys.
+
+        on: the on-key column when it has the same name on both sides;
+            otherwise give `left_on` and `right_on`.  Numeric or temporal.
+        by / left_by + right_by: equality key column(s), a name or a
+            sequence of names.
+        strategy:
+            "backward"  the greatest right key <= the left key; among equal
+                        right keys the one latest in the right input.
+            "forward"   the least right key >= the left key; among equal
+                        right keys the one earliest in the right input.
+            "nearest"   the nearer of the forward match and the backward
+                        match below the left key; a tie goes to the forward
+                        one, the larger key.  Integer and temporal distances
+                        are exact over the whole 64-bit range; float
+                        distances are taken in float64, an equal key has
+                        distance 0 and a NaN distance counts as greatest.
+            The reference engine's pick among equal right keys depends on
+            the order in which right batches arrive; this one is
+            deterministic.
+        prefix, suffix: a right column whose name is already taken is named
+            prefix + name + suffix.
+
+        The result is left-join shaped: every left row once, right columns
+        null where nothing matched.  A null on-key on either side never
+        matches, and neither does a null `by` key (not even another null).
+        NaN on-keys are equal to each other and sort above +inf; -0.0 equals
+        +0.0.
+
+        Raises ValueError when `on` comes with `left_on`/`right_on`, when
+        `on` is absent and a side is missing, when `by` comes with
+        `left_by`/`right_by`, when only one of `left_by`/`right_by` is
+        given or their lengths differ, for an unknown strategy and for an
+        on-key that is neither numeric nor temporal."""
         from .logical.plan import AsofJoin
-        lb = list(left_by or by or [])
-        rb = list(right_by or by or [])
+        if on is not None:
+            if left_on is not None or right_on is not None:
+                raise ValueError(
+                    "If `on` is set then `left_on` and `right_on` must be None")
+            left_on = right_on = on
+        elif left_on is None or right_on is None:
+            raise ValueError(
+                "If `on` is None then both `left_on` and `right_on` must be set")
+
+        def names(v):
+            return [v] if isinstance(v, str) else list(v)
+
+        if by is not None:
+            if left_by is not None or right_by is not None:
+                raise ValueError(
+                    "Cannot specify both `by` and `left_by`/`right_by`")
+            lb = rb = names(by)
+        elif left_by is None and right_by is None:
+            lb = rb = []
+        elif left_by is None or right_by is None:
+            raise ValueError(
+                "Specify both `left_by` and `right_by`, or neither")
+        else:
+            lb, rb = names(left_by), names(right_by)
+            if len(lb) != len(rb):
+                raise ValueError(
+                    "left_by and right_by must have the same number of "
+                    f"columns, got {len(lb)} and {len(rb)}")
         node = AsofJoin(self._builder.plan, other._builder.plan, left_on,
-                        right_on, lb, rb, strategy, suffix)
+                        right_on, list(lb), list(rb), strategy, suffix,
+                        prefix)
+        _ = node.schema  # refuses an unsupported on-key dtype here
         from .logical.builder import LogicalPlanBuilder
         return self._wrap(LogicalPlanBuilder(node))
 

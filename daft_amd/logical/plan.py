@@ -489,22 +489,44 @@ class Join(LogicalPlan):
         return (f"Join({self.how}, on={self.left_on!r}=={self.right_on!r})")
 
 
+ASOF_STRATEGIES = ("backward", "forward", "nearest")
+
+
+def asof_key_supported(dt: DataType) -> bool:
+    """On-key dtypes an as-of join can order: the fixed-width numeric and
+    temporal types that rowops._order_key_u64 encodes."""
+    return (dt.is_boolean() or dt.is_integer() or dt.is_floating()
+            or (dt.is_temporal() and dt.to_physical().is_integer()))
+
+
 class AsofJoin(LogicalPlan):
     """Nearest-key join (ref: LogicalPlan::AsofJoin + join/asof_join.rs)."""
 
     def __init__(self, left: LogicalPlan, right: LogicalPlan, left_on: str,
                  right_on: str, left_by: List[str], right_by: List[str],
-                 strategy: str = "backward", suffix: str = "_right"):
+                 strategy: str = "backward", suffix: str = "_right",
+                 prefix: Optional[str] = None):
         super().__init__([left, right])
+        if strategy not in ASOF_STRATEGIES:
+            raise ValueError(
+                f"join_asof: strategy must be one of {ASOF_STRATEGIES}, "
+                f"got {strategy!r}")
         self.left_on = left_on
         self.right_on = right_on
         self.left_by = left_by
         self.right_by = right_by
         self.strategy = strategy
         self.suffix = suffix
+        self.prefix = prefix
 
     def _compute_schema(self):
         ls, rs = self.children[0].schema, self.children[1].schema
+        for side, sch, name in (("left", ls, self.left_on),
+                                ("right", rs, self.right_on)):
+            if not asof_key_supported(sch[name].dtype):
+                raise ValueError(
+                    f"join_asof: {side} on-key {name!r} has dtype "
+                    f"{sch[name].dtype}; numeric or temporal expected")
         fields = ls.fields()
         taken = set(ls.names())
         skip = set(self.right_by) | {self.right_on}
@@ -513,11 +535,15 @@ class AsofJoin(LogicalPlan):
             if f.name in skip and (f.name in set(self.left_by) or
                                    f.name == self.left_on):
                 continue
-            out = f.name if f.name not in taken else f.name + self.suffix
-            i = 1
-            while out in taken:
-                out = f"{f.name}{self.suffix}{i}"
-                i += 1
+            out = f.name
+            if out in taken:
+                # a clashing right column is prefix + name + suffix
+                base = (self.prefix or "") + f.name + self.suffix
+                out = base
+                i = 1
+                while out in taken:
+                    out = f"{base}{i}"
+                    i += 1
             taken.add(out)
             fields.append(Field(out, f.dtype))
             self._right_cols.append((f.name, out))
@@ -530,7 +556,7 @@ class AsofJoin(LogicalPlan):
     def with_children(self, children):
         return AsofJoin(children[0], children[1], self.left_on,
                         self.right_on, self.left_by, self.right_by,
-                        self.strategy, self.suffix)
+                        self.strategy, self.suffix, self.prefix)
 
     def describe(self):
         return (f"AsofJoin({self.left_on}~{self.right_on}, "

@@ -22,6 +22,7 @@ setup(
                 "csrc/join.hip",
                 "csrc/sort.hip",
                 "csrc/partition.hip",
+                "csrc/asof.hip",
                 "csrc/strings.hip",
                 "csrc/strtransform.hip",
                 "csrc/regex.hip",
