@@ -101,6 +101,26 @@ Tensor asof_probe(Tensor left_keys, Tensor left_gids, Tensor right_keys,
                   int64_t strategy /*0 backward, 1 forward, 2 nearest*/,
                   bool allow_exact, bool float_keys);
 
+// framed window aggregate (window.hip).  Sorted position p holds original row
+// perm[p]; partition g owns sorted positions [seg_offsets[g],
+// seg_offsets[g+1]).  values (float64 or int64; unused by a count) and valid
+// are in original row order, and so are the outputs {value, count}: count is
+// the number of non-null inputs in the row's frame (int64), value the
+// aggregate over them, 0 where count is 0.  value is float64 for mean,
+// variance (population) and stddev and for float64 input, else int64 and
+// exact.  Bounds: kind 0 unbounded, 1 current row + offset, 2 (hi only, with
+// lo unbounded) end of the row's peer run, read from new_peer, a bool per
+// sorted position that is true where a new run of equal order keys starts.
+// Checked on the host: dtype, contiguity, device, rank, lengths, op and
+// bound codes.  The Python wrapper answers for what lives in device memory:
+// perm a permutation, gids below seg_offsets.numel() - 1, monotone offsets
+// from 0 to n that match the sort.
+std::vector<Tensor> window_agg(
+    OptTensor values, OptTensor valid, Tensor perm, Tensor gids,
+    Tensor seg_offsets, OptTensor new_peer, int64_t lo_kind, int64_t lo_off,
+    int64_t hi_kind, int64_t hi_off,
+    int64_t op /*0 sum, 1 count, 2 mean, 3 min, 4 max, 5 variance, 6 stddev*/);
+
 // multimodal (multimodal.hip)
 Tensor simhash(Tensor offsets, Tensor bytes, int64_t ngram_size);
 Tensor minhash(Tensor offsets, Tensor bytes, int64_t num_hashes,

@@ -32,6 +32,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "stable one-pass hash partition -> (perm, counts)");
   m.def("asof_probe", &asof_probe,
         "as-of join probe -> matched right row per left row, or -1");
+  m.def("window_agg", &window_agg,
+        "framed window aggregate by segmented scans -> (value, count)");
   m.def("simhash", &simhash);
   m.def("minhash", &minhash, "word-ngram MinHash signatures (wave/row)");
   m.def("hll_update", &hll_update, "HyperLogLog register updates");

@@ -14,7 +14,7 @@ import torch
 from ..expressions.expressions import Agg, AggKind, ExprNode
 from ..kernels import rowops
 from ..recordbatch import RecordBatch
-from ..schema import DataType, Field, Schema
+from ..schema import DataType, Field, Schema, TypeKind
 from ..series import Series
 from . import agg as agg_mod
 
@@ -92,6 +92,9 @@ def run_window(batch: RecordBatch, window_exprs: List[ExprNode],
         num_groups = 1
 
     sorted_pos = None
+    # sorted partition offsets, built once for the native window kernels
+    seg = _seg_offsets(gids, num_groups) if order_by and gids.is_cuda \
+        else None
     if order_by:
         okeys = [e.evaluate(batch) for e in order_by]
         gseries = Series("__g", DataType.int64(), data=gids)
@@ -118,7 +121,8 @@ def run_window(batch: RecordBatch, window_exprs: List[ExprNode],
                 # (ref: window_partition_and_order_by.rs incremental states)
                 if a.kind in _FRAMEABLE:
                     out_cols.append(_framed_agg(batch, a, nm, gids,
-                                                sorted_pos, order_by, frame))
+                                                sorted_pos, order_by, frame,
+                                                seg))
                     continue
                 raise NotImplementedError(
                     f"window aggregate {a.kind!r} with ORDER BY / frame is "
@@ -135,8 +139,10 @@ def run_window(batch: RecordBatch, window_exprs: List[ExprNode],
             else:
                 okeys = [k.evaluate(batch) for k in order_by]
                 same_as_prev = _same_as_prev(okeys, gids, perm, pos)
-                vals = _rank_values(rn, same_as_prev, gids, perm,
-                                    dense=e.kind == "dense_rank")
+                dense = e.kind == "dense_rank"
+                vals = _rank_native(rn, same_as_prev, gids, perm, seg,
+                                    dense) if seg is not None else \
+                    _rank_values(rn, same_as_prev, gids, perm, dense=dense)
             out_cols.append(Series(nm, DataType.uint64(),
                                    data=vals.view(torch.uint64)))
         elif e.kind in ("first_value", "last_value"):
@@ -184,14 +190,158 @@ _FRAMEABLE = {AggKind.SUM, AggKind.COUNT, AggKind.COUNT_ALL, AggKind.MEAN,
               AggKind.MIN, AggKind.MAX, AggKind.STDDEV, AggKind.VARIANCE}
 
 
+def _seg_offsets(gids: torch.Tensor, num_groups: int) -> torch.Tensor:
+    """[G + 1] offsets: after the (partition id, order keys) sort, partition
+    g owns the sorted positions [seg[g], seg[g + 1])."""
+    seg = torch.zeros(num_groups + 1, dtype=torch.int64, device=gids.device)
+    torch.cumsum(torch.bincount(gids, minlength=num_groups), 0, out=seg[1:])
+    return seg
+
+
+# op and bound codes shared with csrc/window.hip (WinOp, WinBound)
+_WIN_OP = {AggKind.SUM: 0, AggKind.COUNT: 1, AggKind.COUNT_ALL: 1,
+           AggKind.MEAN: 2, AggKind.MIN: 3, AggKind.MAX: 4,
+           AggKind.VARIANCE: 5, AggKind.STDDEV: 6}
+_WIN_UNBOUNDED, _WIN_OFFSET, _WIN_PEER_END = 0, 1, 2
+_SIGNED_VIEW = {torch.uint16: torch.int16, torch.uint32: torch.int32,
+                torch.uint64: torch.int64}
+
+
+def _native_values(data: Optional[torch.Tensor], kind: str):
+    """The value column as the float64 or int64 tensor window_agg takes, or
+    None when the native path does not serve this storage."""
+    if data is None:
+        return None
+    dt = data.dtype
+    if dt in (torch.float32, torch.float64):
+        return data.to(torch.float64)
+    if dt == torch.bool:
+        return None if kind in (AggKind.MIN, AggKind.MAX) \
+            else data.to(torch.int64)
+    if dt in (torch.int8, torch.int16, torch.int32, torch.int64,
+              torch.uint8):
+        return data.to(torch.int64)
+    if dt in (torch.uint16, torch.uint32):
+        return data.view(_SIGNED_VIEW[dt]).to(torch.int64) & \
+            ((1 << (8 * data.element_size())) - 1)
+    return None
+
+
+def _from_i64_or_f64(value: torch.Tensor, tdt: torch.dtype) -> torch.Tensor:
+    if value.dtype == tdt:
+        return value
+    if tdt in _SIGNED_VIEW:
+        return value.to(_SIGNED_VIEW[tdt]).view(tdt)
+    return value.to(tdt)
+
+
+def _native_frame(frame):
+    """(lo_kind, lo_off, hi_kind, hi_off) for window_agg; None for a frame
+    that starts at unbounded_following or ends at unbounded_preceding."""
+    from ..window import Window as W
+    if frame is None:
+        return _WIN_UNBOUNDED, 0, _WIN_PEER_END, 0
+    start, end = frame
+    if start == W.unbounded_following or end == W.unbounded_preceding:
+        return None
+
+    def bound(spec):
+        if spec in (W.unbounded_preceding, W.unbounded_following):
+            return _WIN_UNBOUNDED, 0
+        return _WIN_OFFSET, 0 if spec == W.current_row else int(spec)
+    return bound(start) + bound(end)
+
+
+def _framed_agg_native(batch: RecordBatch, a: Agg, name: str,
+                       gids: torch.Tensor, sorted_pos, order_by, frame,
+                       seg: torch.Tensor) -> Optional[Series]:
+    """_framed_agg on the device: csrc/window.hip scans each partition once
+    forward and/or backward and looks every frame up, exact for integers and
+    without subtracting prefixes.  None when the dtype or the frame is left
+    to the torch code."""
+    from ..kernels import native_required
+    perm, pos, _part_start = sorted_pos
+    n = gids.shape[0]
+    fr = _native_frame(frame)
+    if fr is None:
+        return None
+    vdata = vvalid = None
+    if a.kind != AggKind.COUNT_ALL and a.child is not None:
+        values = a.child.evaluate(batch)
+        if len(values) == 1 and n > 1:
+            values = values.broadcast(n)
+        if values.is_dict():
+            values = values.dict_decode()
+        dt = values.dtype
+        if not (dt.is_floating() or dt.is_integer() or
+                dt.kind == TypeKind.BOOL):
+            return None
+        vdata = _native_values(values.data, a.kind)
+        if vdata is None:
+            return None
+        vdata = vdata.contiguous()
+        if values.validity is not None:
+            vvalid = values.validity.contiguous()
+    new_peer = None
+    if frame is None:
+        okeys = [k.evaluate(batch) for k in order_by]
+        new_peer = (~_same_as_prev(okeys, gids, perm, pos))[perm].contiguous()
+    value, count = native_required().window_agg(
+        vdata, vvalid, perm.contiguous(), gids.contiguous(), seg, new_peer,
+        *fr, _WIN_OP[a.kind])
+
+    if a.kind in (AggKind.COUNT, AggKind.COUNT_ALL):
+        return Series(name, DataType.uint64(), data=count.view(torch.uint64))
+    # a frame that holds its own row and reads no nulls is never empty
+    lo_kind, lo_off, hi_kind, hi_off = fr
+    holds_row = (lo_kind != _WIN_OFFSET or lo_off <= 0) and \
+        (hi_kind != _WIN_OFFSET or hi_off >= 0)
+    validity = None
+    if vvalid is not None or not holds_row:
+        v = count > 0
+        if not bool(v.all().item()):
+            validity = v
+    out_dt = a.to_field(batch.schema).dtype
+    if a.kind in (AggKind.MEAN, AggKind.STDDEV, AggKind.VARIANCE):
+        out_dt = DataType.float64()
+    return Series(name, out_dt,
+                  data=_from_i64_or_f64(value, out_dt.to_torch()),
+                  validity=validity)
+
+
+def _rank_native(rn: torch.Tensor, same_as_prev: torch.Tensor,
+                 gids: torch.Tensor, perm: torch.Tensor, seg: torch.Tensor,
+                 dense: bool) -> torch.Tensor:
+    """_rank_values as one forward scan of window_agg: dense_rank is the
+    running sum of the new-key flag, rank the running max of (position in
+    partition + 1 at key starts, else 0)."""
+    from ..kernels import native_required
+    newkey = ~same_as_prev
+    vals = newkey.to(torch.int64) if dense else \
+        torch.where(newkey, rn + 1, torch.zeros_like(rn))
+    value, _count = native_required().window_agg(
+        vals.contiguous(), None, perm.contiguous(), gids.contiguous(), seg,
+        None, _WIN_UNBOUNDED, 0, _WIN_OFFSET, 0,
+        _WIN_OP[AggKind.SUM if dense else AggKind.MAX])
+    return value
+
+
 def _framed_agg(batch: RecordBatch, a: Agg, name: str, gids: torch.Tensor,
-                sorted_pos, order_by, frame) -> Series:
+                sorted_pos, order_by, frame,
+                seg: Optional[torch.Tensor] = None) -> Series:
     """Windowed aggregate over an explicit ROWS frame, or the SQL
     RANGE-default frame (unbounded preceding .. current row, peers share)
-    when `frame` is None.  sum/count/mean/stddev/variance run on per-
-    partition prefix sums; min/max on a sparse-table range query
+    when `frame` is None.  With `seg` (the partitions' sorted offsets, given
+    for device batches) the native scan kernels serve the dtypes and frames
+    they cover.  Otherwise, and on the CPU, sum/count/mean/stddev/variance
+    run on prefix sums; min/max on a sparse-table range query
     (ref: window_partition_and_dynamic_frame.rs / window_states/minmax.rs).
     All positions are in sorted space; results scatter back through perm."""
+    if seg is not None:
+        out = _framed_agg_native(batch, a, name, gids, sorted_pos, order_by,
+                                 frame, seg)
+        if out is not None:
+            return out
     perm, pos, part_start = sorted_pos
     n = gids.shape[0]
     dev = gids.device

@@ -23,6 +23,7 @@ setup(
                 "csrc/sort.hip",
                 "csrc/partition.hip",
                 "csrc/asof.hip",
+                "csrc/window.hip",
                 "csrc/strings.hip",
                 "csrc/strtransform.hip",
                 "csrc/regex.hip",
