@@ -213,3 +213,29 @@ std::vector<Tensor> regex_spans(Tensor offsets, Tensor bytes, OptTensor valid,
                                 int64_t start, Tensor rev_table,
                                 Tensor rev_flags, int64_t rev_start,
                                 Tensor match_offsets, int64_t limit);
+
+// text <-> values (strparse.hip).  Each parse returns {values, status}:
+// status uint8 [n] is 0 parsed, 1 null (`valid` false; for the numeric targets
+// also the empty row), 2 "the host must decide"; values are 0 where status is
+// not 0.  str_parse_int: [+-]?[0-9]+ in [lo, hi], int64.  str_parse_decimal:
+// int64 scaled by 10^scale, |v| <= max_abs < 10^18, no exponent, no nonzero
+// digit past `scale`.  str_parse_float: float64, correctly rounded or status
+// 2; pow5 is int64 [651, 2], the {low, high} words of the 128-bit powers of
+// five for 10^-342 .. 10^308.  str_parse_datetime: sep 0 reads YYYY-MM-DD as
+// int32 days since 1970-01-01, sep ' ' or 'T' reads YYYY-MM-DD<sep>HH:MM:SS
+// as int64 microseconds.  format_int (int64) and format_date (int32 days in
+// years 0001-9999) return {offsets, bytes}; null rows are empty.
+// strparse_staging switches the LDS staging of the parse kernels on or off
+// and returns the previous setting.
+std::vector<Tensor> str_parse_int(Tensor offsets, Tensor bytes, OptTensor valid,
+                                  int64_t lo, int64_t hi);
+std::vector<Tensor> str_parse_decimal(Tensor offsets, Tensor bytes,
+                                      OptTensor valid, int64_t scale,
+                                      int64_t max_abs);
+std::vector<Tensor> str_parse_float(Tensor offsets, Tensor bytes,
+                                    OptTensor valid, Tensor pow5);
+std::vector<Tensor> str_parse_datetime(Tensor offsets, Tensor bytes,
+                                       OptTensor valid, int64_t sep);
+std::vector<Tensor> format_int(Tensor values, OptTensor valid);
+std::vector<Tensor> format_date(Tensor days, OptTensor valid);
+bool strparse_staging(bool on);

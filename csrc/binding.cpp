@@ -59,6 +59,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("str_reverse", &str_reverse, "reverse by code point");
   m.def("str_normalize_ascii", &str_normalize_ascii,
         "normalize ASCII rows (one wavefront per row), flag the others");
+  m.def("str_parse_int", &str_parse_int,
+        "string -> int64 in [lo, hi] -> (values, status)");
+  m.def("str_parse_decimal", &str_parse_decimal,
+        "string -> int64 scaled by 10^scale -> (values, status)");
+  m.def("str_parse_float", &str_parse_float,
+        "string -> float64, Clinger fast path and Eisel-Lemire -> (values, "
+        "status)");
+  m.def("str_parse_datetime", &str_parse_datetime,
+        "ISO date -> days, or date and time -> microseconds -> (values, "
+        "status)");
+  m.def("format_int", &format_int, "int64 -> decimal text");
+  m.def("format_date", &format_date, "days -> YYYY-MM-DD");
+  m.def("strparse_staging", &strparse_staging,
+        "switch LDS staging of the parse kernels, returns the old setting");
   m.def("levenshtein", &levenshtein,
         "ASCII Levenshtein distance, one thread per row pair");
   m.def("bpe_encode", &bpe_encode,

@@ -1128,11 +1128,8 @@ class StringNamespace(_Namespace):
 
 
 def _str_to_date(s: Series, fmt: str) -> Series:
-    vals = s.cpu().to_pylist()
-    out = [None if v is None else _dt.datetime.strptime(v, fmt).date()
-           for v in vals]
-    res = Series.from_pylist(s.name, out, DataType.date())
-    return res.to(s.device) if s.is_gpu() else res
+    from ..kernels import parse
+    return parse.strptime_column(s, fmt, DataType.date())
 
 
 class TemporalNamespace(_Namespace):

@@ -188,6 +188,11 @@ def try_cast(x, dtype):
     """Cast that yields null instead of raising (string->numeric etc.)."""
     def run(s: Series) -> Series:
         from .. import kernels
+        from ..kernels import parse
+        d = s.dict_decode() if s.is_dict() and s.is_gpu() else s
+        if parse.device_target(d, dtype):
+            # the kernels' status says which rows need the salvage loop
+            return parse.try_parse_cast(d, dtype)
         try:
             return kernels.cast(s, dtype)
         except Exception:

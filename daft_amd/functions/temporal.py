@@ -330,10 +330,7 @@ def total_nanoseconds(x):
 
 def to_datetime(x, fmt: str = "%Y-%m-%d %H:%M:%S"):
     def run(s: Series) -> Series:
-        vals = s.cpu().to_pylist()
-        out = [None if v is None else _dt.datetime.strptime(v, fmt)
-               for v in vals]
-        r = Series.from_pylist(s.name, out, DataType.timestamp("us"))
-        return r.to(s.device) if s.is_gpu() else r
+        from ..kernels import parse
+        return parse.strptime_column(s, fmt, DataType.timestamp("us"))
     return Expression(ScalarFn("to_datetime", run, [_to_node(x)],
                                DataType.timestamp("us")))

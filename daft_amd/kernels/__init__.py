@@ -309,6 +309,7 @@ def concat(series: List[Series]) -> Series:
 # ---------------------------------------------------------------------------
 
 def cast(s: Series, dtype: DataType) -> Series:
+    from . import parse
     if s.dtype == dtype:
         return s
     if s.is_dict():
@@ -420,25 +421,13 @@ def cast(s: Series, dtype: DataType) -> Series:
             out = data.to(tdt)
         return Series(s.name, dtype, data=out, validity=s.validity)
     if nk == TypeKind.STRING:
-        # host-side stringification (display path, not hot)
-        vals = s.to_pylist()
-        out = [None if v is None else _to_str(v) for v in vals]
-        return Series.from_pylist(s.name, out, DataType.string(),
-                                  device=s.device)
-    if k == TypeKind.STRING and dtype.is_numeric():
-        vals = s.to_pylist()
-        if dtype.is_decimal():
-            conv = lambda x: x  # Decimal(str) parse in from_pylist: exact
-        elif dtype.is_floating():
-            conv = float
-        else:
-            conv = int
-        out = [None if v is None or v == "" else conv(v) for v in vals]
-        return Series.from_pylist(s.name, out, dtype, device=s.device)
-    if k == TypeKind.STRING and nk == TypeKind.DATE:
-        vals = s.to_pylist()
-        out = [None if v is None else _dt_parse_date(v) for v in vals]
-        return Series.from_pylist(s.name, out, dtype, device=s.device)
+        # integers and dates of a device column: format kernels; else host
+        return parse.to_string(s)
+    if k == TypeKind.STRING and (dtype.is_numeric() or nk == TypeKind.DATE):
+        # device column: parse kernels, the rows they flag go to the host
+        if parse.device_target(s, dtype):
+            return parse.parse_cast(s, dtype)
+        return parse._host_parse(s, dtype)
     if k == TypeKind.LIST and nk == TypeKind.LIST:
         child = s.children[0].cast(dtype.inner)
         return Series(s.name, dtype, offsets=s.offsets, children=[child],
@@ -483,19 +472,6 @@ def cast(s: Series, dtype: DataType) -> Series:
         return Series(s.name, dtype, offsets=offs, children=[child],
                       validity=s.validity)
     raise TypeError(f"unsupported cast {s.dtype!r} -> {dtype!r}")
-
-
-def _to_str(v) -> str:
-    if isinstance(v, float):
-        return repr(v)
-    if isinstance(v, bytes):
-        return v.decode("utf-8", "replace")
-    return str(v)
-
-
-def _dt_parse_date(v: str):
-    import datetime as dtmod
-    return dtmod.date.fromisoformat(v)
 
 
 # ---------------------------------------------------------------------------

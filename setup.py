@@ -26,6 +26,7 @@ setup(
                 "csrc/window.hip",
                 "csrc/strings.hip",
                 "csrc/strtransform.hip",
+                "csrc/strparse.hip",
                 "csrc/regex.hip",
                 "csrc/multimodal.hip",
                 "csrc/fusedexpr.hip",
