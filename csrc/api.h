@@ -150,6 +150,21 @@ std::vector<Tensor> fused_eval_jit(const std::string& src,
                                    std::vector<int64_t> out_codes,
                                    std::vector<int64_t> out_need_valid,
                                    int64_t n);
+// Filter -> Aggregate in one JIT kernel.  `body` is the straight-line row
+// code; ops[a] is the AggOp of accumulator a and own_valid[a] says whether
+// its input can be null.  Returns {acc f64 [A*G], cnt i64 [A*G], hit i64 [G]},
+// slot of (a, g) at a * G + g; hit counts the rows that pass per group.
+// fused_agg_source is host-only: the full kernel text for that plan.
+std::string fused_agg_source(const std::string& body,
+                             std::vector<int64_t> col_has_valid,
+                             std::vector<int64_t> ops,
+                             std::vector<int64_t> own_valid, int64_t groups);
+std::vector<Tensor> fused_agg_jit(const std::string& body,
+                                  std::vector<Tensor> cols,
+                                  std::vector<OptTensor> valids,
+                                  std::vector<int64_t> ops,
+                                  std::vector<int64_t> own_valid,
+                                  int64_t groups, int64_t n);
 
 // BPE tokenize (bpe.hip)
 std::vector<Tensor> bpe_encode(Tensor offsets, Tensor bytes, Tensor byte2id,

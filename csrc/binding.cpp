@@ -80,6 +80,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_jit_available", &fused_jit_available);
   m.def("fused_eval_jit", &fused_eval_jit,
         "hipRTC-compiled straight-line fused expression kernel");
+  m.def("fused_agg_jit", &fused_agg_jit,
+        "hipRTC-compiled filter + grouped aggregate in one pass");
+  m.def("fused_agg_source", &fused_agg_source,
+        "kernel text fused_agg_jit compiles for a plan (host only)");
   m.def("fused_eval", &fused_eval,
         "fused stack-interpreter expression evaluation (one kernel per "
         "projection list)");

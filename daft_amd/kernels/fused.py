@@ -911,6 +911,203 @@ def plan_jit(exprs: List[ExprNode], batch) -> Optional[JitPlan]:
                    out_meta, len(batch))
 
 
+# ---------------------------------------------------------------------------
+# Filter -> Aggregate in one kernel (csrc/fusedjit.hip, fused_agg_jit): the
+# predicate, the group slot and every aggregate input become the row body of
+# an aggregating skeleton that lives with the launcher
+# ---------------------------------------------------------------------------
+
+SCAN_AGG_MAX_SLOTS = 2048   # groups x aggregates, _multi_agg's staging bound
+SCAN_AGG_MAX_ACCS = 16      # kAggMaxAccs in csrc/fusedjit.hip
+_ACC_SUM, _ACC_MIN, _ACC_MAX, _ACC_COUNT = 0, 1, 2, 3   # AggOp in csrc/api.h
+
+
+class ScanAggPlan:
+    """Host-side plan of one fused Filter -> Aggregate pass.
+
+    `ops[a]` / `own_valid[a]` describe accumulator a; `agg_acc[k]` is the
+    accumulator the k-th named aggregate reads (None: the per-group hit
+    count); `keys` are the key Series (dictionary-coded or bool) with
+    `cards` their cardinalities, packed first key major."""
+    __slots__ = ("body", "cols", "ops", "own_valid", "groups", "keys",
+                 "cards", "agg_acc", "n")
+
+    def __init__(self, body, cols, ops, own_valid, groups, keys, cards,
+                 agg_acc, n):
+        self.body = body
+        self.cols = cols
+        self.ops = ops
+        self.own_valid = own_valid
+        self.groups = groups
+        self.keys = keys
+        self.cards = cards
+        self.agg_acc = agg_acc
+        self.n = n
+
+    def source(self) -> str:
+        """Full kernel text (needs the native library, no device)."""
+        from . import native_required
+        return native_required().fused_agg_source(
+            self.body, [int(s.validity is not None) for s in self.cols],
+            self.ops, self.own_valid, self.groups)
+
+
+def _scan_agg_key(e: ExprNode, batch):
+    """(Series, cardinality) of a key whose range is known without a pass
+    over the data: a dictionary-coded or bool column without validity."""
+    base = e
+    while isinstance(base, Alias):
+        base = base.child
+    if not isinstance(base, ColumnRef):
+        raise _Bail("computed key")
+    s = e.evaluate(batch)
+    if s.validity is not None or s.data is None or len(s) != len(batch) or \
+            not s.data.is_contiguous():
+        raise _Bail("key with validity")
+    if s.is_dict() and s.data.dtype == torch.int32:
+        return s, len(s.children[0])
+    if s.dtype.is_boolean() and s.data.dtype == torch.bool and \
+            not s.children and s.pyobjs is None:
+        return s, 2
+    raise _Bail(f"key dtype {s.dtype}")
+
+
+def plan_scan_agg(batch, pred: Optional[ExprNode], groupby: List[ExprNode],
+                  named_aggs) -> Optional[ScanAggPlan]:
+    """Host-only: the row body and accumulator layout for `named_aggs`
+    (name, Agg) over `batch` filtered by `pred` and grouped by `groupby`,
+    or None when the shape keeps the general path."""
+    from ..expressions.expressions import AggKind
+    n = len(batch)
+    if n == 0 or not named_aggs:
+        return None
+    low = _Lower(batch)
+    cg = _CodeGen(low)
+    try:
+        keys, cards = [], []
+        for e in groupby:
+            s, card = _scan_agg_key(e, batch)
+            keys.append(s)
+            cards.append(card)
+        groups = 1
+        for c in cards:
+            groups *= c
+        if groups < 1 or groups * len(named_aggs) > SCAN_AGG_MAX_SLOTS:
+            return None
+
+        passes = []
+        if pred is not None:
+            root = low.lower(pred)
+            if _pk(root.dt) != _K.BOOL:
+                raise _Bail("non-bool predicate")
+            val, vld = cg.gen(root)
+            passes = [f"({val})"] + ([f"({vld})"] if vld else [])
+
+        # accumulators: one per distinct (input, op); MEAN reads its SUM,
+        # COUNT the counter of any accumulator over the same input
+        accs: Dict[Tuple[str, int], int] = {}
+        acc_in: List[Tuple[str, Optional[str]]] = []
+        ops: List[int] = []
+        by_input: Dict[str, int] = {}
+        agg_acc: List[Optional[int]] = [None] * len(named_aggs)
+        lowered = []
+        for _name, a in named_aggs:
+            if a.kind == AggKind.COUNT_ALL or (a.kind == AggKind.COUNT and
+                                               a.child is None):
+                lowered.append(None)
+                continue
+            if a.kind not in (AggKind.SUM, AggKind.MEAN, AggKind.MIN,
+                              AggKind.MAX, AggKind.COUNT):
+                raise _Bail(f"aggregate {a.kind}")
+            root = low.lower(a.child)
+            if _pk(root.dt) not in (_K.FLOAT32, _K.FLOAT64):
+                raise _Bail("non-float aggregate input")
+            val, vld = cg.gen(root)
+            lowered.append((root.key, f"(double)({val})", vld))
+
+        def acc_for(key, val, vld, op):
+            ix = accs.get((key, op))
+            if ix is None:
+                ix = accs[(key, op)] = len(ops)
+                ops.append(op)
+                acc_in.append((val, vld))
+                by_input.setdefault(key, ix)
+            return ix
+
+        kind_op = {AggKind.SUM: _ACC_SUM, AggKind.MEAN: _ACC_SUM,
+                   AggKind.MIN: _ACC_MIN, AggKind.MAX: _ACC_MAX}
+        for k, (_name, a) in enumerate(named_aggs):
+            if lowered[k] is not None and a.kind in kind_op:
+                agg_acc[k] = acc_for(*lowered[k], kind_op[a.kind])
+        for k, (_name, a) in enumerate(named_aggs):
+            if lowered[k] is not None and a.kind == AggKind.COUNT:
+                key, val, vld = lowered[k]
+                if vld is None:
+                    continue          # never null: the group's hit count
+                ix = by_input.get(key)
+                agg_acc[k] = ix if ix is not None else \
+                    acc_for(key, "0.0", vld, _ACC_COUNT)
+        if not ops:
+            # counts only: one counting accumulator keeps the layout whole
+            ops.append(_ACC_COUNT)
+            acc_in.append(("0.0", None))
+        if len(ops) > SCAN_AGG_MAX_ACCS:
+            return None
+    except _Bail:
+        return None
+
+    lines = list(cg.lines)
+    slot = "0"
+    for j, (s, card) in enumerate(zip(keys, cards)):
+        ix = len(low.cols)
+        low.cols.append(s)
+        if s.is_dict():
+            lines.append(f"      const int k{j} = ((const int*)C{ix}d)[i];")
+        else:
+            lines.append(f"      const int k{j} = ((const unsigned char*)"
+                         f"C{ix}d)[i] != 0;")
+        # a code outside the vocabulary joins no group
+        passes.append(f"((unsigned int)k{j} < {card}u)")
+        slot = f"({slot}) * {card} + k{j}"
+    if not low.cols:
+        return None       # a bare count(*): nothing to scan
+    for s in low.cols:
+        if not s.data.is_contiguous() or (
+                s.validity is not None and
+                (s.validity.dtype != torch.bool or
+                 not s.validity.is_contiguous() or
+                 s.validity.numel() != n)):
+            return None
+    lines.append("      const bool fa_pass = %s;" %
+                 (" && ".join(passes) if passes else "true"))
+    lines.append(f"      const int fa_slot = {slot};")
+    lines.append("      const double fa_v[FA_A] = {%s};" %
+                 ", ".join(v for v, _ in acc_in))
+    lines.append("      const bool fa_ok[FA_A] = {%s};" %
+                 ", ".join(vv if vv else "true" for _, vv in acc_in))
+    return ScanAggPlan("\n".join(lines) + "\n", list(low.cols), ops,
+                       [int(vv is not None) for _, vv in acc_in], groups,
+                       keys, cards, agg_acc, n)
+
+
+def scan_agg_enabled() -> bool:
+    import os
+    return not (os.environ.get("DAFT_AMD_DISABLE_FUSED") or
+                os.environ.get("DAFT_AMD_DISABLE_JIT") or
+                os.environ.get("DAFT_AMD_DISABLE_FUSED_AGG"))
+
+
+def run_scan_agg(plan: ScanAggPlan):
+    """Launch `plan`: (acc f64 [A, G], cnt i64 [A, G], hit i64 [G])."""
+    from . import native_required
+    a = len(plan.ops)
+    acc, cnt, hit = native_required().fused_agg_jit(
+        plan.body, [s.data for s in plan.cols],
+        [s.validity for s in plan.cols], plan.ops, plan.own_valid,
+        plan.groups, plan.n)
+    return acc.view(a, plan.groups), cnt.view(a, plan.groups), hit
+
+
 def try_fuse_jit(exprs: List[ExprNode], batch) -> Optional[List]:
     """hipRTC path: compile the list to a straight-line kernel.  Returns
     the full result list or None (caller falls back to the interpreter)."""

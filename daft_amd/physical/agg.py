@@ -457,27 +457,88 @@ def _multi_agg(batch, gids, num_groups, named_aggs, mask):
                                          ops)
     out = out.view(len(named_aggs), num_groups)
     cnt = cnt.view(len(named_aggs), num_groups)
-    cols = []
-    for i, (cname, a, values) in enumerate(meta):
-        k = a.kind
-        if k in (AggKind.COUNT, AggKind.COUNT_ALL):
-            cols.append(Series(cname, DataType.uint64(),
-                               data=cnt[i].contiguous()
-                               .view(torch.uint64)))
-            continue
-        c = cnt[i]
-        validity = c > 0
-        if bool(validity.all()):
-            validity = None
-        if k == AggKind.MEAN:
-            data = out[i] / c.clamp(min=1).to(torch.float64)
-            cols.append(Series(cname, DataType.float64(),
-                               data=data.contiguous(), validity=validity))
-            continue
-        out_dt = a.to_field(batch.schema).dtype
-        data = out[i].contiguous().to(out_dt.to_torch())
-        cols.append(Series(cname, out_dt, data=data, validity=validity))
-    return cols
+    return [_slot_series(cname, a, out[i], cnt[i], batch.schema)
+            for i, (cname, a, _values) in enumerate(meta)]
+
+
+def _slot_series(cname, a, out, c, schema, all_valid=None) -> Series:
+    """Output column of aggregate `a` from its accumulator row `out` (f64
+    per group) and valid-row counts `c`.  `all_valid` spares the read-back
+    when the caller already knows whether every group has a valid row."""
+    k = a.kind
+    if k in (AggKind.COUNT, AggKind.COUNT_ALL):
+        return Series(cname, DataType.uint64(),
+                      data=c.contiguous().view(torch.uint64))
+    validity = c > 0
+    if bool(validity.all()) if all_valid is None else all_valid:
+        validity = None
+    if k == AggKind.MEAN:
+        data = out / c.clamp(min=1).to(torch.float64)
+        return Series(cname, DataType.float64(), data=data.contiguous(),
+                      validity=validity)
+    out_dt = a.to_field(schema).dtype
+    data = out.contiguous().to(out_dt.to_torch())
+    return Series(cname, out_dt, data=data, validity=validity)
+
+
+def _finish_aggregate(key_cols, agg_cols, residuals, num_groups):
+    inter = RecordBatch(key_cols + agg_cols, num_rows=num_groups)
+    out_cols = list(key_cols)
+    for r in residuals:
+        out_cols.append(r.evaluate(inter))
+    return RecordBatch(out_cols, num_rows=num_groups)
+
+
+def try_fused_scan_agg(batch: RecordBatch, pred: Optional[ExprNode],
+                       groupby: List[ExprNode], aggs: List[ExprNode]
+                       ) -> Optional[RecordBatch]:
+    """Filter -> Aggregate as ONE pass over the input (kernels/fused.py,
+    plan_scan_agg): no mask, no group ids, no materialised value columns.
+    Returns what `_prep` + `run_aggregate` return for the same arguments, or
+    None when the shape keeps that path (see plan_scan_agg)."""
+    from ..kernels import fused, load_native
+    if batch.device.type != "cuda" or len(batch) == 0 or \
+            not fused.scan_agg_enabled():
+        return None
+    nat = load_native()
+    if nat is None or not hasattr(nat, "fused_agg_jit"):
+        return None
+    named_aggs, residuals = decompose_agg_exprs(aggs)
+    plan = fused.plan_scan_agg(batch, pred, groupby, named_aggs)
+    if plan is None:
+        return None
+    acc, cnt, hit = fused.run_scan_agg(plan)
+    n_acc, groups = cnt.shape
+    # the one read-back: counts and hits, A*G + G numbers
+    host = torch.cat([cnt.reshape(-1), hit]).cpu()
+    cnt_h, hit_h = host[:n_acc * groups].view(n_acc, groups), host[-groups:]
+    key_cols = []
+    if groupby:
+        # live slots in ascending packed-code order, as the dense path
+        keep_h = torch.nonzero(hit_h > 0).reshape(-1)
+        keep = keep_h.to(batch.device)
+        acc, cnt, hit = acc[:, keep], cnt[:, keep], hit[keep]
+        cnt_h = cnt_h[:, keep_h]
+        stride = groups
+        for s, card in zip(plan.keys, plan.cards):
+            stride //= card
+            codes = (keep // stride) % card
+            if s.is_dict():
+                key_cols.append(Series.make_dict(s.name, s.children[0],
+                                                 codes))
+            else:
+                key_cols.append(Series(s.name, s.dtype,
+                                       data=codes.to(torch.bool)))
+        groups = int(keep_h.numel())
+    agg_cols = []
+    for (cname, a), ix in zip(named_aggs, plan.agg_acc):
+        if ix is None:
+            agg_cols.append(_slot_series(cname, a, None, hit, batch.schema))
+        else:
+            agg_cols.append(_slot_series(
+                cname, a, acc[ix], cnt[ix], batch.schema,
+                all_valid=bool((cnt_h[ix] > 0).all())))
+    return _finish_aggregate(key_cols, agg_cols, residuals, groups)
 
 
 def run_aggregate(batch: RecordBatch, groupby: List[ExprNode],
@@ -506,12 +567,7 @@ def run_aggregate(batch: RecordBatch, groupby: List[ExprNode],
         agg_cols = [compute_agg(batch, gids, num_groups, cname, a,
                                 mask=mask)
                     for cname, a in named_aggs]
-    inter = RecordBatch(key_cols + agg_cols,
-                        num_rows=num_groups)
-    out_cols = list(key_cols)
-    for r in residuals:
-        out_cols.append(r.evaluate(inter))
-    out = RecordBatch(out_cols, num_rows=num_groups)
+    out = _finish_aggregate(key_cols, agg_cols, residuals, num_groups)
     if mask is not None and groupby:
         # drop groups whose rows were all masked out.  NOT a torch
         # scatter_add: 600M atomic adds onto a handful of group slots

@@ -524,6 +524,15 @@ class AggregateOp(PhysicalOp):
             return b.take(compact_indices(ms), has_neg=False), None
         return b, mask.contiguous()
 
+    def _aggregate(self, b, pred, aggs):
+        """Aggregate one batch under `pred`: the one-pass scan kernel where
+        the shape allows it, else mask (or compact) and aggregate."""
+        out = agg_mod.try_fused_scan_agg(b, pred, self.groupby, aggs)
+        if out is not None:
+            return out
+        b, mask = self._prep(b, pred)
+        return agg_mod.run_aggregate(b, self.groupby, aggs, mask=mask)
+
     def execute(self, ectx) -> BatchIter:
         from itertools import chain as _chain
         pred, child = self._fusion_pred()
@@ -533,9 +542,7 @@ class AggregateOp(PhysicalOp):
         if second is None:
             batch = first if first is not None else RecordBatch.empty(
                 child.schema, device=ectx.device)
-            batch, mask = self._prep(batch, pred)
-            yield agg_mod.run_aggregate(batch, self.groupby, self.aggs,
-                                        mask=mask)
+            yield self._aggregate(batch, pred, self.aggs)
             return
         # multiple input batches: fold each into per-group partial states
         # (same partial/final decomposition the distributed planner uses)
@@ -562,9 +569,7 @@ class AggregateOp(PhysicalOp):
         gnames = [e.to_field(cschema).name for e in self.groupby]
         parts = []
         for b in _chain([first, second], it):
-            b, mask = self._prep(b, pred)
-            parts.append(agg_mod.run_aggregate(b, self.groupby, partials,
-                                               mask=mask))
+            parts.append(self._aggregate(b, pred, partials))
         merged = RecordBatch.concat(parts)
         final = agg_mod.run_aggregate(
             merged, [ColumnRef(n) for n in gnames], final_named)
