@@ -85,6 +85,14 @@ Tensor u64_mod(Tensor hashes, int64_t n_partitions);
 std::vector<Tensor> hash_partition(Tensor hashes, int64_t num_partitions,
                                    bool remix);
 
+// top-k candidate selection (topk.hip), an MSD radix select.
+// keys: int64 [n] holding u64 order keys (unsigned compare), 1 <= k <= n.
+// T = the k-th smallest key.  Returns {rows, stats}:
+//   rows  int64 [m], ascending: every i with keys[i] <= T  (m >= k)
+//   stats int64 [3]: {T as bit pattern, #keys < T, #keys == T}
+// Checked on the host: dtype, contiguity, device, rank, 1 <= k <= n.
+std::vector<Tensor> topk_candidates(Tensor keys, int64_t k);
+
 // as-of probe (asof.hip).  Keys are order-preserving u64 bit patterns held in
 // int64 (rowops._order_key_u64).  The right side is already filtered to usable
 // rows and stably sorted by (group, key).  Group g owns sorted positions

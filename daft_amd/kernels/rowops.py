@@ -863,17 +863,24 @@ def _stable_sort_perm_by(keys: torch.Tensor) -> torch.Tensor:
     return torch.from_numpy(np.argsort(u, kind="stable").astype(np.int64))
 
 
+def _dict_rank_key(s: Series) -> torch.Tensor:
+    """Order-preserving key of a dictionary string column: each row's code
+    replaced by the rank of its vocab entry (the tiny vocab is argsorted
+    once)."""
+    vocab = s.children[0]
+    vperm = argsort_multi([vocab], [False], [False])
+    rank = torch.empty(len(vocab), dtype=torch.int64, device=s.device)
+    rank[vperm] = torch.arange(len(vocab), dtype=torch.int64,
+                               device=s.device)
+    return rank[s.data.to(torch.int64)]
+
+
 def _key_bits(s: Series):
     """(biased int64 key ascending-ordered, bit width) or None when the
     column can't compose into a packed radix key."""
     if s.is_dict():
-        vocab = s.children[0]
-        vperm = argsort_multi([vocab], [False], [False])
-        rank = torch.empty(len(vocab), dtype=torch.int64, device=s.device)
-        rank[vperm] = torch.arange(len(vocab), dtype=torch.int64,
-                                   device=s.device)
-        k = rank[s.data.to(torch.int64)]
-        card = max(len(vocab), 1)
+        k = _dict_rank_key(s)
+        card = max(len(s.children[0]), 1)
         return k, max(card - 1, 1).bit_length()
     dt = s.dtype
     if not (dt.is_integer() or dt.is_boolean() or dt.is_temporal()):
@@ -971,14 +978,7 @@ def argsort_multi(keys: Sequence[Series], descending: Sequence[bool],
     # LSD over keys: sort by last key first
     for s, desc, nf in list(zip(keys, descending, nulls_first))[::-1]:
         if s.is_dict():
-            # order-preserving code ranks: argsort the (tiny) vocab once
-            vocab = s.children[0]
-            vperm = argsort_multi([vocab], [False], [False])
-            rank = torch.empty(len(vocab), dtype=torch.int64,
-                               device=s.device)
-            rank[vperm] = torch.arange(len(vocab), dtype=torch.int64,
-                                       device=s.device)
-            perm = _value_pass(s, rank[s.data.to(torch.int64)], desc, perm)
+            perm = _value_pass(s, _dict_rank_key(s), desc, perm)
         elif s.dtype.kind in (TypeKind.STRING, TypeKind.BINARY):
             if _has_nul_byte(s):
                 # chunk keys are zero padded, so "a" and "a\0" tie on every
@@ -1000,6 +1000,102 @@ def argsort_multi(keys: Sequence[Series], descending: Sequence[bool],
                              torch.full_like(perm, null_key))
             perm = perm[_stable_sort_perm_by(nk[perm])]
     return perm
+
+
+# ---------------------------------------------------------------------------
+# top-k: prune by a radix select on the leading key, sort the survivors
+# ---------------------------------------------------------------------------
+
+# Gate of the select path, from benchmarks/bench_topn.py on an MI355X with
+# n = 2^10 .. 2^24 and k = n/64 .. n/2 (int64, float64+date and string keys).
+# Below 2^16 rows both paths are launch overhead and the full sort is ahead
+# or level (0.85x-0.95x at 2^10..2^14, mixed at 2^15); from 2^16 on the
+# select wins every run on all three shapes (1.4x at 2^16, 2.9x at 2^18, 15x
+# at 2^27 for k <= 10^4).  At k = n/8 it still wins everywhere (1.04x at the
+# worst point, strings at 2^22); at k = n/4 it loses or ties at 2^21.
+_TOPK_MIN_ROWS = 1 << 16
+_TOPK_MAX_FRACTION = 8       # select only while k * this <= n
+
+
+def topk_candidates(keys: torch.Tensor,
+                    k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(rows, stats) for u64 order keys held as int64, 1 <= k <= n: with T
+    the k-th smallest key (unsigned), `rows` lists every i with
+    keys[i] <= T in ascending order and `stats` is int64
+    [T's bit pattern, #keys < T, #keys == T].  Device keys go through the
+    radix select of csrc/topk.hip; host keys through numpy."""
+    n = keys.numel()
+    if not 1 <= k <= n:
+        raise ValueError(f"k must be in [1, {n}], got {k}")
+    if keys.is_cuda:
+        rows, stats = native_required().topk_candidates(keys.contiguous(), k)
+        return rows, stats
+    u = keys.numpy().view(np.uint64)
+    t = np.partition(u, k - 1)[k - 1]
+    stats = np.array([t.view(np.int64), np.count_nonzero(u < t),
+                      np.count_nonzero(u == t)], dtype=np.int64)
+    return (torch.from_numpy(np.flatnonzero(u <= t).astype(np.int64)),
+            torch.from_numpy(stats))
+
+
+def _leading_image(s: Series, desc: bool,
+                   nulls_first: bool) -> Optional[torch.Tensor]:
+    """A non-strict order-preserving map of a first sort key into u64 (int64
+    bit pattern): a row that sorts before or level with another never has
+    the larger image.  Collisions (strings equal in their first 8 bytes, a
+    valid row on the null sentinel) only add ties.  None when the type has
+    no such image here."""
+    kind = s.dtype.kind
+    if s.is_dict():
+        img = _dict_rank_key(s)
+    elif kind in (TypeKind.STRING, TypeKind.BINARY):
+        img = _string_chunk_key(s, 0)
+    elif s.dtype.is_decimal() and s.children:
+        from . import decimal128 as d128
+        img = d128.limbs(s)[1] ^ _SIGN64           # high limb, signed
+    elif s.data is not None and s.data.dim() == 1 and (
+            kind == TypeKind.BOOL or _phys_float(s.dtype)
+            or s.dtype.is_integer() or s.dtype.is_temporal()
+            or s.dtype.is_decimal()):
+        img = _order_key_u64(s)
+    else:
+        return None
+    if desc:
+        img = ~img
+    if s.validity is not None:
+        img = torch.where(s.validity, img,
+                          torch.full_like(img, 0 if nulls_first else -1))
+    return img
+
+
+def _topk_select(keys: Sequence[Series], descending: Sequence[bool],
+                 nulls_first: Sequence[bool], k: int) -> Optional[torch.Tensor]:
+    """argsort_multi(...)[:k] for 1 <= k <= n without sorting every row.
+    Every row of the true first k has a leading-key image at or below the
+    k-th smallest image T, and topk_candidates returns all such rows in
+    ascending row order, so a stable sort of just those rows reproduces the
+    full sort's first k, ties included.  None when the leading key has no
+    image."""
+    img = _leading_image(keys[0], descending[0], nulls_first[0])
+    if img is None:
+        return None
+    rows, _stats = topk_candidates(img, k)
+    sub = [s.take(rows, has_neg=False) for s in keys]
+    return rows[argsort_multi(sub, descending, nulls_first)[:k]]
+
+
+def topk_multi(keys: Sequence[Series], descending: Sequence[bool],
+               nulls_first: Sequence[bool], k: int) -> torch.Tensor:
+    """Exactly argsort_multi(keys, descending, nulls_first)[:k].  Large
+    device inputs with a small k are pruned by the radix select first."""
+    n = len(keys[0])
+    k = max(int(k), 0)
+    if (0 < k and n >= _TOPK_MIN_ROWS and k * _TOPK_MAX_FRACTION <= n
+            and all(_is_gpu(s) for s in keys)):
+        top = _topk_select(keys, descending, nulls_first, k)
+        if top is not None:
+            return top
+    return argsort_multi(keys, descending, nulls_first)[:k]
 
 
 # ---------------------------------------------------------------------------

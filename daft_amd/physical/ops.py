@@ -717,9 +717,8 @@ class TopNOp(PhysicalOp):
             if len(rb) <= k:
                 return rb
             keys = [e.evaluate(rb) for e in self.by]
-            perm = rowops.argsort_multi(keys, self.descending,
-                                        self.nulls_first)
-            return rb.take(perm[:k])
+            return rb.take(rowops.topk_multi(keys, self.descending,
+                                             self.nulls_first, k))
 
         acc: Optional[RecordBatch] = None
         for rb in self.children[0].execute_tracked(ectx):
@@ -732,7 +731,7 @@ class TopNOp(PhysicalOp):
             yield RecordBatch.empty(self.schema, device=ectx.device)
             return
         keys = [e.evaluate(acc) for e in self.by]
-        perm = rowops.argsort_multi(keys, self.descending, self.nulls_first)
+        perm = rowops.topk_multi(keys, self.descending, self.nulls_first, k)
         yield acc.take(perm[self.offset:k])
 
 

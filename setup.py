@@ -22,6 +22,7 @@ setup(
                 "csrc/join.hip",
                 "csrc/sort.hip",
                 "csrc/partition.hip",
+                "csrc/topk.hip",
                 "csrc/asof.hip",
                 "csrc/window.hip",
                 "csrc/strings.hip",
