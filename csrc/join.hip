@@ -12,6 +12,7 @@
 #include <limits>
 
 #include "common.h"
+#include "block_rank.h"
 #include "host_args.h"
 #include "row_ops.h"
 #include "api.h"
@@ -68,12 +69,14 @@ DEV_INLINE int32_t dense_lookup(const K* keys, const bool* valid, int64_t i,
 // The looked-up rows are kept (4 B per probe row) so that the fill pass
 // streams them back and the table is read once per probe row: with random
 // keys over a table beyond L2 the lookup is what the pass costs.
+// counts has a leading 0 and block b's count at [b + 1], so one inclusive
+// scan of it gives every block's exclusive base and, last, the total.
 template <typename K>
 __global__ void dense_count_kernel(const K* keys, const bool* valid,
                                    int64_t n, int64_t chunk, int64_t mn,
                                    int64_t mx, const int32_t* table,
                                    bool anti, int32_t* rows,
-                                   int64_t* counts) {
+                                   int64_t* counts /*[nblocks + 1]*/) {
   int64_t begin = (int64_t)blockIdx.x * chunk;
   int64_t end = min(begin + chunk, n);
   int32_t local = 0;
@@ -83,30 +86,25 @@ __global__ void dense_count_kernel(const K* keys, const bool* valid,
     rows[i] = row;
     local += ((row >= 0) != anti);
   }
-  __shared__ int32_t acc;
-  if (threadIdx.x == 0) acc = 0;
-  __syncthreads();
-  for (int off = WAVE / 2; off; off >>= 1)
-    local += __shfl_down(local, off, WAVE);
-  if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(&acc, local);
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = acc;
+  int32_t total = block_sum(local);
+  if (threadIdx.x == 0) {
+    counts[blockIdx.x + 1] = total;
+    if (blockIdx.x == 0) counts[0] = 0;
+  }
 }
 
-// Fill pass: same chunks, kJoinUnroll tiles per trip, ballot rank within the
-// wave and wave totals through LDS, so output order is row order.
-// rows is what the count pass looked up; incl is the inclusive scan of
+// Fill pass: same chunks, kJoinUnroll tiles per trip under one barrier
+// (block_rank.h compaction slots), so output order is row order.
+// rows is what the count pass looked up; block_base is the scan of its
 // counts; ridx is null for semi/anti.
 __global__ void dense_fill_kernel(const int32_t* rows, int64_t n,
                                   int64_t chunk, bool anti,
-                                  const int64_t* incl, const int64_t* counts,
-                                  int64_t* lidx, int64_t* ridx) {
+                                  const int64_t* block_base, int64_t* lidx,
+                                  int64_t* ridx) {
   int64_t begin = (int64_t)blockIdx.x * chunk;
   int64_t end = min(begin + chunk, n);
   __shared__ int32_t wave_counts[kJoinUnroll][kJoinWaves];
-  int64_t base = incl[blockIdx.x] - counts[blockIdx.x];
-  int lane = threadIdx.x & (WAVE - 1);
-  int wid = threadIdx.x / WAVE;
+  int64_t base = block_base[blockIdx.x];
   for (int64_t tile = begin; tile < end;
        tile += (int64_t)kJoinUnroll * kJoinBlock) {
     int32_t row[kJoinUnroll];
@@ -121,29 +119,21 @@ __global__ void dense_fill_kernel(const int32_t* rows, int64_t n,
     for (int u = 0; u < kJoinUnroll; ++u) {
       // -2 marks a row past the end: selected by no mode
       sel[u] = anti ? row[u] == -1 : row[u] >= 0;
-      uint64_t ballot = __ballot(sel[u]);
-      rank[u] = __popcll(ballot & ((1ull << lane) - 1));
-      if (lane == 0) wave_counts[u][wid] = __popcll(ballot);
+      int wtotal;
+      rank[u] = wave_rank(sel[u], &wtotal);
+      wave_total_put(wave_counts[u], wtotal);
     }
     __syncthreads();
-    int64_t pos = base;
 #pragma unroll
     for (int u = 0; u < kJoinUnroll; ++u) {
-      int before = 0, total = 0;
-#pragma unroll
-      for (int w = 0; w < kJoinWaves; ++w) {
-        int c = wave_counts[u][w];
-        before += w < wid ? c : 0;
-        total += c;
-      }
+      WaveSpan w = wave_span<kJoinWaves>(wave_counts[u]);
       if (sel[u]) {
-        int64_t o = pos + before + rank[u];
+        int64_t o = base + w.before + rank[u];
         lidx[o] = tile + u * kJoinBlock + threadIdx.x;
         if (ridx) ridx[o] = row[u];
       }
-      pos += total;
+      base += w.total;
     }
-    base = pos;  // every thread keeps the same running base
     __syncthreads();
   }
 }
@@ -219,24 +209,21 @@ static std::vector<Tensor> dense_probe_t(const Tensor& keys,
     return {lidx, ridx};
   }
   bool anti = mode == JOIN_ANTI;
-  int64_t tile = (int64_t)kJoinUnroll * kJoinBlock;
-  int64_t chunk = (n + kMaxBlocks - 1) / kMaxBlocks;
-  chunk = (chunk + tile - 1) / tile * tile;
-  int nblocks = (int)((n + chunk - 1) / chunk);
-  auto counts = torch::empty({nblocks}, opts64);
+  constexpr int64_t tile = (int64_t)kJoinUnroll * kJoinBlock;
+  auto [chunk, nblocks] = block_chunks(n, tile, tile);
+  auto counts = torch::empty({nblocks + 1}, opts64);
   auto rows = torch::empty({n}, torch::dtype(torch::kInt32).device(dev));
   hipLaunchKernelGGL(dense_count_kernel<K>, dim3(nblocks), dim3(kJoinBlock),
                      0, cur_stream(), kp, valid, n, chunk, mn, mx, tp, anti,
                      rows.data_ptr<int32_t>(), counts.data_ptr<int64_t>());
-  auto incl = torch::cumsum(counts, 0);
-  int64_t total = incl[nblocks - 1].item<int64_t>();
+  auto base = torch::cumsum(counts, 0);
+  int64_t total = base[nblocks].item<int64_t>();
   auto lidx = torch::empty({total}, opts64);
   auto ridx = torch::empty({mode == JOIN_INNER ? total : 0}, opts64);
   if (total > 0)
     hipLaunchKernelGGL(dense_fill_kernel, dim3(nblocks), dim3(kJoinBlock), 0,
                        cur_stream(), rows.data_ptr<int32_t>(), n, chunk, anti,
-                       incl.data_ptr<int64_t>(), counts.data_ptr<int64_t>(),
-                       lidx.data_ptr<int64_t>(),
+                       base.data_ptr<int64_t>(), lidx.data_ptr<int64_t>(),
                        mode == JOIN_INNER ? ridx.data_ptr<int64_t>()
                                           : nullptr);
   return {lidx, ridx};

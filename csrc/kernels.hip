@@ -8,6 +8,7 @@
 //  * low-cardinality aggregations stage per-block accumulators in LDS
 //    (160 KiB/CU) and emit one global atomic per block per group
 #include "common.h"
+#include "block_rank.h"
 #include "host_args.h"
 #include "row_ops.h"
 #include "api.h"
@@ -68,8 +69,10 @@ Tensor hash_rows(const std::vector<int64_t>& tags,
 
 // ---------------------------------------------------------------------------
 // stream compaction: bool mask -> selected indices
-// (ballot + wave prefix within block, block offsets via device cumsum)
+// (block_rank.h steps within a block, block offsets via device cumsum)
 // ---------------------------------------------------------------------------
+
+constexpr int kCompactBlock = 256;
 
 __global__ void block_count_kernel(const bool* mask, int64_t n,
                                    int64_t chunk, int32_t* counts) {
@@ -78,45 +81,26 @@ __global__ void block_count_kernel(const bool* mask, int64_t n,
   int32_t local = 0;
   for (int64_t i = begin + threadIdx.x; i < end; i += blockDim.x)
     local += mask[i] ? 1 : 0;
-  __shared__ int32_t acc;
-  if (threadIdx.x == 0) acc = 0;
-  __syncthreads();
-  // wave reduce then one atomic per wave
-  for (int off = WAVE / 2; off; off >>= 1)
-    local += __shfl_down(local, off, WAVE);
-  if ((threadIdx.x & (WAVE - 1)) == 0) atomicAdd(&acc, local);
-  __syncthreads();
-  if (threadIdx.x == 0) counts[blockIdx.x] = acc;
+  int32_t total = block_sum(local);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
 __global__ void compact_kernel(const bool* mask, int64_t n, int64_t chunk,
                                const int32_t* block_offsets, int64_t* out) {
   int64_t begin = (int64_t)blockIdx.x * chunk;
   int64_t end = min(begin + chunk, n);
-  __shared__ int64_t base;
-  __shared__ int32_t wave_counts[256 / WAVE];
-  if (threadIdx.x == 0) base = block_offsets[blockIdx.x];
-  __syncthreads();
-  int lane = threadIdx.x & (WAVE - 1);
-  int wid = threadIdx.x / WAVE;
-  int nwaves = blockDim.x / WAVE;
-  for (int64_t tile = begin; tile < end; tile += blockDim.x) {
+  __shared__ int32_t wave_counts[kCompactBlock / WAVE];
+  int64_t base = block_offsets[blockIdx.x];
+  for (int64_t tile = begin; tile < end; tile += kCompactBlock) {
     int64_t i = tile + threadIdx.x;
     bool sel = i < end && mask[i];
-    uint64_t ballot = __ballot(sel);
-    int rank = __popcll(ballot & ((1ull << lane) - 1));
-    int wtotal = __popcll(ballot);
-    if (lane == 0) wave_counts[wid] = wtotal;
+    int wtotal;
+    int rank = wave_rank(sel, &wtotal);
+    wave_total_put(wave_counts, wtotal);
     __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wid; ++w) woff += wave_counts[w];
-    if (sel) out[base + woff + rank] = i;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int t = 0;
-      for (int w = 0; w < nwaves; ++w) t += wave_counts[w];
-      base += t;
-    }
+    WaveSpan w = wave_span<kCompactBlock / WAVE>(wave_counts);
+    if (sel) out[base + w.before + rank] = i;
+    base += w.total;
     __syncthreads();
   }
 }
@@ -127,10 +111,8 @@ Tensor compact_indices(Tensor mask) {
   int64_t n = mask.numel();
   auto dev = mask.device();
   if (n == 0) return torch::empty({0}, torch::dtype(torch::kInt64).device(dev));
-  int block = 256;
-  int64_t chunk = (n + kMaxBlocks - 1) / kMaxBlocks;
-  if (chunk < block) chunk = block;
-  int nblocks = (int)((n + chunk - 1) / chunk);
+  int block = kCompactBlock;
+  auto [chunk, nblocks] = block_chunks(n, block);
   auto counts = torch::empty({nblocks},
                              torch::dtype(torch::kInt32).device(dev));
   hipLaunchKernelGGL(block_count_kernel, dim3(nblocks), dim3(block), 0,

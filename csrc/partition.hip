@@ -1,8 +1,8 @@
 // Stable one-pass hash partitioner (gfx950): groups rows into P <= 256
 // partitions by `hash % P` with one histogram kernel and one scatter kernel.
-// That is a single radix digit, so it follows radix_hist_kernel /
-// radix_scatter_kernel in sort.hip (same block decomposition, same ballot
-// ranking) with these differences:
+// That is a single radix digit: the block decomposition and the stable digit
+// scatter are the steps of block_rank.h, which one pass of the sort
+// (sort.hip) uses too.  Against that pass:
 //   - the partition id is computed in registers in both kernels and never
 //     written to memory;
 //   - the scatter reads only the hashes and writes only perm[pos] = row
@@ -13,6 +13,7 @@
 // Used by the grace hash join, RepartitionOp and the RCCL exchange through
 // rowops.hash_partition.
 #include "common.h"
+#include "block_rank.h"
 #include "host_args.h"
 #include "api.h"
 
@@ -39,18 +40,6 @@ DEV_INLINE int part_id(uint64_t h, const PartSpec s) {
   return (int)(((hi % s.p) * s.two32 + lo % s.p) % s.p);
 }
 
-// Lanes of this wave that are active and hold the same id as the caller.
-// Every lane of the wave must call it (ballots are wave-wide).
-DEV_INLINE uint64_t part_peers(int d, bool active, int bits) {
-  uint64_t peers = __ballot(active);
-  for (int b = 0; b < bits; ++b) {
-    bool bit = (d >> b) & 1;
-    uint64_t vote = __ballot(bit);
-    peers &= bit ? vote : ~vote;
-  }
-  return peers;
-}
-
 // hist[b][d] = rows of block b's chunk that fall in partition d.  A wave
 // adds one count per distinct id, so a skewed input does not serialise on
 // one LDS counter.
@@ -63,13 +52,12 @@ __global__ void partition_hist_kernel(const uint64_t* hashes, int64_t n,
   __syncthreads();
   int64_t begin = (int64_t)blockIdx.x * chunk;
   int64_t end = min(begin + chunk, n);
-  int lane = threadIdx.x & (WAVE - 1);
-  uint64_t lane_lt = (1ull << lane) - 1;
+  uint64_t lane_lt = lane_lt_mask();
   for (int64_t tile = begin; tile < end; tile += PART_BLOCK) {
     int64_t i = tile + threadIdx.x;
     bool active = i < end;
     int d = active ? part_id(hashes[i], spec) : 0;
-    uint64_t peers = part_peers(d, active, spec.bits);
+    uint64_t peers = wave_peers(d, active, spec.bits);
     if (active && (peers & lane_lt) == 0)
       atomicAdd(&lhist[d], __popcll(peers));
   }
@@ -79,9 +67,8 @@ __global__ void partition_hist_kernel(const uint64_t* hashes, int64_t n,
 }
 
 // Stable scatter: block b owns rows [b*chunk, (b+1)*chunk), walked as
-// 256-row tiles.  running[d] is the next free slot of partition d for this
-// block; within a tile a row's slot is running[d] + rows of earlier waves
-// with id d + its rank among its wave's peers.
+// 256-row tiles (block_rank.h, digit scatter).  running[d] is the next free
+// slot of partition d for this block.
 __global__ void partition_scatter_kernel(const uint64_t* hashes, int64_t n,
                                          int64_t chunk, PartSpec spec,
                                          const int64_t* offsets /*[nb][p]*/,
@@ -93,32 +80,14 @@ __global__ void partition_scatter_kernel(const uint64_t* hashes, int64_t n,
     running[d] = offsets[(int64_t)blockIdx.x * P + d];
   int64_t begin = (int64_t)blockIdx.x * chunk;
   int64_t end = min(begin + chunk, n);
-  int lane = threadIdx.x & (WAVE - 1);
-  int wid = threadIdx.x / WAVE;
-  uint64_t lane_lt = (1ull << lane) - 1;
   for (int64_t tile = begin; tile < end; tile += PART_BLOCK) {
-    for (int d = threadIdx.x; d < P; d += blockDim.x)
-      for (int w = 0; w < PART_NWAVES; ++w) wave_hist[w][d] = 0;
-    __syncthreads();
+    digit_tile_begin<PART_MAX, PART_NWAVES>(P, wave_hist);
     int64_t i = tile + threadIdx.x;
     bool active = i < end;
     int d = active ? part_id(hashes[i], spec) : 0;
-    uint64_t peers = part_peers(d, active, spec.bits);
-    int rank_in_wave = __popcll(peers & lane_lt);
-    if (active && rank_in_wave == 0) wave_hist[wid][d] = __popcll(peers);
-    __syncthreads();
-    if (active) {
-      int32_t before = 0;
-      for (int w = 0; w < wid; ++w) before += wave_hist[w][d];
-      perm[running[d] + before + rank_in_wave] = i;
-    }
-    __syncthreads();
-    for (int d2 = threadIdx.x; d2 < P; d2 += blockDim.x) {
-      int32_t t = 0;
-      for (int w = 0; w < PART_NWAVES; ++w) t += wave_hist[w][d2];
-      running[d2] += t;
-    }
-    __syncthreads();
+    int64_t pos = digit_tile_pos(d, active, spec.bits, running, wave_hist);
+    if (active) perm[pos] = i;
+    digit_tile_end<PART_MAX, PART_NWAVES>(P, running, wave_hist);
   }
 }
 
@@ -145,11 +114,9 @@ std::vector<Tensor> hash_partition(Tensor hashes, int64_t num_partitions,
   spec.pow2 = (num_partitions & (num_partitions - 1)) == 0;
   spec.remix = remix;
 
-  int64_t chunk = (n + kMaxBlocks - 1) / kMaxBlocks;
-  if (chunk < PART_BLOCK) chunk = PART_BLOCK;
+  auto [chunk, nblocks] = block_chunks(n, PART_BLOCK);
   // a block counts its chunk in int32 LDS cells
   TORCH_CHECK(chunk <= INT32_MAX, "hash_partition: too many rows");
-  int nblocks = (int)((n + chunk - 1) / chunk);
   auto stream = cur_stream();
   const uint64_t* hp = (const uint64_t*)hashes.data_ptr<int64_t>();
 

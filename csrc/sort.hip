@@ -9,6 +9,7 @@
 // stable passes (kernels/rowops.py argsort_multi), so this kernel only ever
 // sorts u64.
 #include "common.h"
+#include "block_rank.h"
 #include "host_args.h"
 #include "api.h"
 
@@ -34,8 +35,8 @@ __global__ void radix_hist_kernel(const uint64_t* keys, int64_t n,
 }
 
 // Stable scatter: block b owns input range [b*chunk, (b+1)*chunk), processed
-// as sequential 256-element tiles.  Within a tile, each lane finds its rank
-// among equal digits via 8 ballot rounds; cross-wave offsets via LDS.
+// as sequential 256-element tiles (block_rank.h, digit scatter).  Output
+// positions are int32: the sort is limited to 2^31 rows.
 __global__ void radix_scatter_kernel(const uint64_t* keys_in,
                                      const int64_t* vals_in, int64_t n,
                                      int64_t chunk, int shift,
@@ -47,42 +48,18 @@ __global__ void radix_scatter_kernel(const uint64_t* keys_in,
     running[d] = offsets[(int64_t)blockIdx.x * RADIX + d];
   int64_t begin = (int64_t)blockIdx.x * chunk;
   int64_t end = min(begin + chunk, n);
-  int lane = threadIdx.x & (WAVE - 1);
-  int wid = threadIdx.x / WAVE;
-  uint64_t lane_lt = (lane == 63) ? ~0ull >> 1 : ((1ull << lane) - 1);
   for (int64_t tile = begin; tile < end; tile += BLOCK) {
-    for (int d = threadIdx.x; d < RADIX; d += blockDim.x)
-      for (int w = 0; w < NWAVES; ++w) wave_hist[w][d] = 0;
-    __syncthreads();
+    digit_tile_begin<RADIX, NWAVES>(RADIX, wave_hist);
     int64_t i = tile + threadIdx.x;
     bool active = i < end;
     uint64_t k = active ? keys_in[i] : 0;
     int d = (int)((k >> shift) & 0xFF);
-    // peers: lanes in this wave with the same digit (among active lanes)
-    uint64_t peers = __ballot(active);
-    for (int b = 0; b < 8; ++b) {
-      bool bit = (d >> b) & 1;
-      uint64_t vote = __ballot(bit);
-      peers &= bit ? vote : ~vote;
-    }
-    int rank_in_wave = __popcll(peers & lane_lt);
-    int wave_count = __popcll(peers);
-    if (active && rank_in_wave == 0) wave_hist[wid][d] = wave_count;
-    __syncthreads();
+    int64_t pos = digit_tile_pos(d, active, 8, running, wave_hist);
     if (active) {
-      int32_t before = 0;
-      for (int w = 0; w < wid; ++w) before += wave_hist[w][d];
-      int64_t pos = running[d] + before + rank_in_wave;
       keys_out[pos] = k;
       vals_out[pos] = vals_in[i];
     }
-    __syncthreads();
-    for (int dd = threadIdx.x; dd < RADIX; dd += blockDim.x) {
-      int32_t t = 0;
-      for (int w = 0; w < NWAVES; ++w) t += wave_hist[w][dd];
-      running[dd] += t;
-    }
-    __syncthreads();
+    digit_tile_end<RADIX, NWAVES>(RADIX, running, wave_hist);
   }
 }
 
@@ -95,9 +72,7 @@ Tensor radix_argsort(Tensor keys) {
   auto vals = torch::arange(n, opts64);
   if (n <= 1) return vals;
 
-  int64_t chunk = (n + kMaxBlocks - 1) / kMaxBlocks;
-  if (chunk < BLOCK) chunk = BLOCK;
-  int nblocks = (int)((n + chunk - 1) / chunk);
+  auto [chunk, nblocks] = block_chunks(n, BLOCK);
 
   auto keys_a = keys.clone();
   auto keys_b = torch::empty_like(keys_a);

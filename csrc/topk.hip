@@ -27,16 +27,17 @@
 // wave usually share one digit (a long run of equal keys, a heavy bin).  The
 // wave takes the digit of its first participating lane, and all lanes that
 // hold it are added with one atomicAdd of the ballot popcount; the remaining
-// lanes add 1 each.  That is two ballots per key slot.  partition.hip's
-// part_peers ranks every distinct digit, which would take 11 ballot rounds
-// here and buys nothing for spread-out digits, where LDS atomics do not
-// collide anyway.
+// lanes add 1 each.  That is two ballots per key slot.  wave_peers
+// (block_rank.h) ranks every distinct digit, which would take 11 ballot
+// rounds here and buys nothing for spread-out digits, where LDS atomics do
+// not collide anyway.
 //
-// Block decomposition follows partition.hip: block b owns rows
-// [b * chunk, (b + 1) * chunk) and all row arithmetic is int64, so the row
-// count is not capped at 2^31.  chunk is even, so every block starts on a
-// 16-byte boundary and a thread loads two keys at a time.
+// Block decomposition, block counts and compaction slots are the steps of
+// block_rank.h; all row arithmetic is int64, so the row count is not capped
+// at 2^31.  chunk is even, so every block starts on a 16-byte boundary and a
+// thread loads two keys at a time.
 #include "common.h"
+#include "block_rank.h"
 #include "host_args.h"
 #include "api.h"
 
@@ -133,10 +134,9 @@ __global__ void topk_span_kernel(const uint64_t* keys, int64_t n,
     a &= (uint64_t)__shfl_xor((unsigned long long)a, off);
     o |= (uint64_t)__shfl_xor((unsigned long long)o, off);
   }
-  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  if (lane == 0) {
-    wand[wid] = a;
-    wor[wid] = o;
+  if (lane_id() == 0) {
+    wand[wave_id()] = a;
+    wor[wave_id()] = o;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -180,7 +180,7 @@ __global__ void topk_hist_kernel(const uint64_t* keys, int64_t n,
   __syncthreads();
   int64_t begin = (int64_t)blockIdx.x * chunk;
   int64_t end = min(begin + chunk, n);
-  int lane = threadIdx.x & (WAVE - 1);
+  int lane = lane_id();
   for (int64_t tile = begin; tile < end; tile += TOPK_TILE) {
     KeyPair p = load_pair(keys, tile + 2 * threadIdx.x, end);
     topk_count_digit(lhist, (int)((p.k0 >> shift) & (TOPK_BINS - 1)),
@@ -237,7 +237,6 @@ __global__ void topk_pick_kernel(TopkState* s, int64_t* hist) {
 __global__ void topk_count_kernel(const uint64_t* keys, int64_t n,
                                   int64_t chunk, const TopkState* s,
                                   int64_t* cnt /*[nblocks]*/) {
-  __shared__ int32_t wtot[TOPK_NWAVES];
   const uint64_t T = s->threshold;
   int64_t begin = (int64_t)blockIdx.x * chunk;
   int64_t end = min(begin + chunk, n);
@@ -246,20 +245,13 @@ __global__ void topk_count_kernel(const uint64_t* keys, int64_t n,
     KeyPair p = load_pair(keys, tile + 2 * threadIdx.x, end);
     mine += (int)(p.a0 && p.k0 <= T) + (int)(p.a1 && p.k1 <= T);
   }
-  for (int off = WAVE / 2; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
-  if ((threadIdx.x & (WAVE - 1)) == 0) wtot[threadIdx.x / WAVE] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t total = 0;
-    for (int w = 0; w < TOPK_NWAVES; ++w) total += wtot[w];
-    cnt[blockIdx.x] = total;
-  }
+  int32_t total = block_sum(mine);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = total;
 }
 
 // Stable write: rows[base[b] ..] = the block's rows with key <= T, in row
-// order.  A lane's slot is the block's running position + rows of earlier
-// waves of the tile + rows of earlier lanes (two ballots, one per key slot).
-// wtot is double-buffered by tile parity, so one barrier per tile is enough.
+// order (two ballots, one per key slot).  wtot is double-buffered by tile
+// parity, so one barrier per tile is enough.
 __global__ void topk_write_kernel(const uint64_t* keys, int64_t n,
                                   int64_t chunk, const TopkState* s,
                                   const int64_t* base /*[nblocks]*/,
@@ -268,29 +260,23 @@ __global__ void topk_write_kernel(const uint64_t* keys, int64_t n,
   const uint64_t T = s->threshold;
   int64_t begin = (int64_t)blockIdx.x * chunk;
   int64_t end = min(begin + chunk, n);
-  int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-  uint64_t lane_lt = (1ull << lane) - 1;
   int64_t run = base[blockIdx.x];
   int buf = 0;
   for (int64_t tile = begin; tile < end; tile += TOPK_TILE, buf ^= 1) {
     int64_t i = tile + 2 * threadIdx.x;
     KeyPair p = load_pair(keys, i, end);
     bool f0 = p.a0 && p.k0 <= T, f1 = p.a1 && p.k1 <= T;
-    uint64_t b0 = __ballot(f0), b1 = __ballot(f1);
-    if (lane == 0) wtot[buf][wid] = __popcll(b0) + __popcll(b1);
+    int t0, t1;
+    int r0 = wave_rank(f0, &t0), r1 = wave_rank(f1, &t1);
+    wave_total_put(wtot[buf], t0 + t1);
     __syncthreads();
-    int32_t before = 0, total = 0;
-    for (int w = 0; w < TOPK_NWAVES; ++w) {
-      if (w < wid) before += wtot[buf][w];
-      total += wtot[buf][w];
-    }
-    int64_t pos = run + before + __popcll(b0 & lane_lt) +
-                  __popcll(b1 & lane_lt);
+    WaveSpan w = wave_span<TOPK_NWAVES>(wtot[buf]);
+    int64_t pos = run + w.before + r0 + r1;
     // pos < m whenever the counts agree with the state; the check keeps a
     // disagreement from writing past the buffer
     if (f0 && pos < m) rows[pos] = i;
     if (f1 && pos + f0 < m) rows[pos + f0] = i + 1;
-    run += total;
+    run += w.total;
   }
 }
 
@@ -306,12 +292,9 @@ std::vector<Tensor> topk_candidates(Tensor keys, int64_t k) {
     keys = keys.clone();
   auto opts64 = torch::dtype(torch::kInt64).device(keys.device());
 
-  int64_t chunk = (n + kMaxBlocks - 1) / kMaxBlocks;
-  if (chunk < TOPK_TILE) chunk = TOPK_TILE;
-  chunk += chunk & 1;
+  auto [chunk, nblocks] = block_chunks(n, TOPK_TILE, 2);
   // a block counts its chunk in int32 LDS cells
   TORCH_CHECK(chunk <= INT32_MAX - 1, who, ": too many rows");
-  int nblocks = (int)((n + chunk - 1) / chunk);
   auto stream = cur_stream();
   const uint64_t* kp = (const uint64_t*)keys.data_ptr<int64_t>();
 
