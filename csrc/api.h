@@ -262,3 +262,35 @@ std::vector<Tensor> str_parse_datetime(Tensor offsets, Tensor bytes,
 std::vector<Tensor> format_int(Tensor values, OptTensor valid);
 std::vector<Tensor> format_date(Tensor days, OptTensor valid);
 bool strparse_staging(bool on);
+
+// CSV structure of one chunk (csv.hip): `data` uint8 [n], n < 2^31, 16-byte
+// aligned, beginning at a record start.  csv_structure returns {sepmask int16
+// [ceil(n / 4096) * 256] (bit i of entry k: byte 16 k + i is a delim or '\n'
+// outside quotes), tile_base int32 [ceil(n / 4096)] (separators before each
+// 4096-byte tile), info int32 [8]}.  info: [0] error bits (1 irregular quote,
+// 2 invalid UTF-8, 4 ragged, 8 blank line, 16 a '\r' outside quotes that no
+// '\n' follows), [1] UTF-8 continuation bytes claimed minus present (0 in a
+// valid chunk), [2] position of the last '\n' separator + 1, [3] the
+// separator count S, [4] 1 when the chunk ends inside quotes.  csv_emit
+// returns sep_pos int32 [S] in byte order and fills info[2] and the ragged
+// and blank-line bits for records of `ncols` fields.  csv_field_lens
+// returns {seg_start int64 [nsel, nrows], lens int64 [nsel, nrows], any_quoted
+// int32 [nsel]} for rows [row0, row0 + nrows) of the columns `cols`: where a
+// field's content starts in `data`, its length once outer quotes are dropped
+// and "" is read as one quote, and whether any field of the column is quoted.
+// csv_extract writes one column's bytes for offsets out_offsets int64
+// [nrows + 1] ending in `total`; `quoted` is the column's any_quoted.
+// csv_precheck turns status 0 into 2 where pyarrow's CSV converters differ
+// from str_parse_*: kind 0 signed integer (leading '+'), 1 unsigned integer
+// (leading '+' or '-'), 2 decimal (more fractional digits than `scale`).
+std::vector<Tensor> csv_structure(Tensor data, int64_t delim);
+Tensor csv_emit(Tensor data, Tensor sepmask, Tensor tile_base, Tensor info,
+                int64_t S, int64_t ncols);
+std::vector<Tensor> csv_field_lens(Tensor data, Tensor sep_pos, int64_t ncols,
+                                   int64_t row0, int64_t nrows,
+                                   std::vector<int64_t> cols);
+Tensor csv_extract(Tensor data, Tensor sep_pos, int64_t ncols, int64_t row0,
+                   int64_t col, Tensor seg_start, Tensor out_offsets,
+                   int64_t total, bool quoted);
+void csv_precheck(Tensor offsets, Tensor bytes, Tensor status, int64_t kind,
+                  int64_t scale);

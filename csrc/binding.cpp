@@ -75,6 +75,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("format_date", &format_date, "days -> YYYY-MM-DD");
   m.def("strparse_staging", &strparse_staging,
         "switch LDS staging of the parse kernels, returns the old setting");
+  m.def("csv_structure", &csv_structure,
+        "CSV chunk -> (separator masks, tile bases, info): quote parity by "
+        "ballots, UTF-8 and quote checks");
+  m.def("csv_emit", &csv_emit,
+        "separator positions in byte order, row shape check");
+  m.def("csv_field_lens", &csv_field_lens,
+        "content start and unescaped length of the selected columns' fields");
+  m.def("csv_extract", &csv_extract,
+        "one column's bytes: segment copy, or unescape where quoted");
+  m.def("csv_precheck", &csv_precheck,
+        "status 0 -> 2 where pyarrow's CSV converters differ");
   m.def("levenshtein", &levenshtein,
         "ASCII Levenshtein distance, one thread per row pair");
   m.def("bpe_encode", &bpe_encode,

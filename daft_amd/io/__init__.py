@@ -201,7 +201,11 @@ def read_ipc(path, columns: Optional[List[str]] = None,
 
 def read_csv(path, has_headers: bool = True, delimiter: str = ",",
              schema: Optional[Dict[str, DataType]] = None,
-             io_config=None, **kwargs) -> DataFrame:
+             io_config=None, device_decode: Optional[bool] = None,
+             **kwargs) -> DataFrame:
+    """`device_decode`: None or True decode local, uncompressed files on the
+    execution device when it is a GPU (kernels/csv.py); False, a CPU device,
+    and compressed or remote inputs are decoded by pyarrow on the host."""
     from . import readers
     paths = _expand_paths(path)
     read_options = {"has_headers": has_headers, "delimiter": delimiter}
@@ -210,6 +214,9 @@ def read_csv(path, has_headers: bool = True, delimiter: str = ",",
     else:
         sch = readers.infer_schema(paths[0], "csv", read_options,
                                    storage_options=io_config)
+    read_options["device_decode"] = device_decode
+    # the device decoder types its columns by the scan schema
+    read_options["schema"] = {f.name: f.dtype for f in sch}
     return DataFrame(LogicalPlanBuilder.from_scan(
         sch, paths, "csv", storage_options=io_config,
         read_options=read_options))

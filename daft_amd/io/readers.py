@@ -5,6 +5,7 @@ GPU-side page decode is a later-round upgrade."""
 from __future__ import annotations
 
 import json as _json
+import os
 from typing import Iterator, List, Optional
 
 from ..recordbatch import RecordBatch
@@ -69,7 +70,7 @@ def infer_schema(path: str, file_format: str,
 def read_file(path: str, file_format: str, columns: Optional[List[str]],
               predicate, limit: Optional[int], storage_options: dict,
               read_options: dict, device,
-              row_groups=None) -> Iterator[RecordBatch]:
+              row_groups=None, raw=None) -> Iterator[RecordBatch]:
     # hive-partitioned scan: key=value path columns attach as constants
     hive_vals = None
     hive_fields = None
@@ -87,7 +88,7 @@ def read_file(path: str, file_format: str, columns: Optional[List[str]],
         from ..series import Series
         for rb in read_file_inner(path_open, file_format, columns,
                                   predicate, limit, read_options, device,
-                                  row_groups):
+                                  row_groups, raw):
             cols = list(rb.columns)
             for n, dt in (hive_fields or []):
                 cols.append(Series.from_pylist(
@@ -96,12 +97,14 @@ def read_file(path: str, file_format: str, columns: Optional[List[str]],
             yield type(rb)(cols, num_rows=len(rb))
         return
     yield from read_file_inner(path_open, file_format, columns, predicate,
-                               limit, read_options, device, row_groups)
+                               limit, read_options, device, row_groups, raw)
 
 
 def read_file_inner(path, file_format, columns, predicate, limit,
                     read_options, device,
-                    row_groups=None) -> Iterator[RecordBatch]:
+                    row_groups=None, raw=None) -> Iterator[RecordBatch]:
+    """`raw` is a csv file's content where a prefetching thread has read it
+    for the device decoder."""
     if file_format == "parquet":
         yield from _read_parquet(path, columns, limit, device, predicate,
                                  row_groups=row_groups)
@@ -114,7 +117,12 @@ def read_file_inner(path, file_format, columns, predicate, limit,
                               if c in tbl.column_names])
         yield RecordBatch.from_arrow(tbl, device=device)
     elif file_format == "csv":
-        yield from _read_csv(path, columns, read_options, device)
+        from ..kernels import csv as device_csv
+        if device_csv.eligible(path, read_options, device):
+            yield from device_csv.read_file_device(path, columns,
+                                                   read_options, device, raw)
+        else:
+            yield from _read_csv(path, columns, read_options, device)
     elif file_format == "json":
         yield from _read_json(path, columns, device)
     elif file_format == "warc":
@@ -190,10 +198,26 @@ def read_files_prefetch(paths: List[str], file_format: str,
 
     tasks = plan_scan_tasks(paths, file_format, storage_options)
 
+    def device_csv_file(pth):
+        from ..kernels import csv as device_csv
+        return file_format == "csv" and device_csv.eligible(
+            _open_input(pth, storage_options), read_options, device)
+
     def load(task):
         tpaths, rgs = task
         out = []
         for pth in tpaths:
+            if device_csv_file(pth):
+                # the thread only reads the bytes; the consuming thread
+                # decodes them on the device.  A file beyond one block is
+                # not held whole: the consumer streams it in blocks.
+                from ..kernels import csv as device_csv
+                raw = None
+                if os.path.getsize(pth) <= device_csv.BLOCK_BYTES:
+                    with open(pth, "rb") as f:
+                        raw = f.read()
+                out.append((pth, raw))
+                continue
             out.extend(read_file(pth, file_format, columns, predicate,
                                  None, storage_options, read_options,
                                  "cpu", row_groups=rgs))
@@ -213,7 +237,11 @@ def read_files_prefetch(paths: List[str], file_format: str,
             if p is not None:
                 pending.append(ex.submit(load, p))
             for rb in batches:
-                if str(device) == "cpu":
+                if isinstance(rb, tuple):
+                    yield from read_file(rb[0], file_format, columns,
+                                         predicate, None, storage_options,
+                                         read_options, device, raw=rb[1])
+                elif str(device) == "cpu":
                     yield rb
                 else:
                     # pinned-staged async H2D on the copy stream so the
@@ -260,7 +288,8 @@ def _open_maybe_compressed(path):
     return path
 
 
-def _read_csv(path, columns, read_options, device) -> Iterator[RecordBatch]:
+def _read_csv(path, columns, read_options, device,
+              column_types=None) -> Iterator[RecordBatch]:
     import pyarrow as pa
     import pyarrow.csv as pacsv
     ro = read_options or {}
@@ -269,8 +298,9 @@ def _read_csv(path, columns, read_options, device) -> Iterator[RecordBatch]:
         autogenerate_column_names=not ro.get("has_headers", True),
         block_size=64 * 1024 * 1024)
     parse_opts = pacsv.ParseOptions(delimiter=ro.get("delimiter", ","))
-    convert = pacsv.ConvertOptions(include_columns=columns) if columns \
-        else None
+    convert = pacsv.ConvertOptions(include_columns=columns or None,
+                                   column_types=column_types) \
+        if columns or column_types else None
     with pacsv.open_csv(path, read_options=read_opts,
                         parse_options=parse_opts,
                         convert_options=convert) as reader:

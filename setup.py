@@ -28,6 +28,7 @@ setup(
                 "csrc/strings.hip",
                 "csrc/strtransform.hip",
                 "csrc/strparse.hip",
+                "csrc/csv.hip",
                 "csrc/regex.hip",
                 "csrc/multimodal.hip",
                 "csrc/fusedexpr.hip",
