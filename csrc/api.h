@@ -294,3 +294,33 @@ Tensor csv_extract(Tensor data, Tensor sep_pos, int64_t ncols, int64_t row0,
                    int64_t total, bool quoted);
 void csv_precheck(Tensor offsets, Tensor bytes, Tensor status, int64_t kind,
                   int64_t scale);
+
+// Parquet page decode (parquet.hip).  `buf` uint8, 16-byte aligned, holds a
+// row group's uploaded column-chunk bytes and the decompression arena behind
+// them; `desc` int64 [pages, 12] is the page table laid out at the top of
+// parquet.hip; `status` int32 [pages] collects 1 (a descriptor outside `buf`
+// or the outputs) and 2 (malformed page content) and is never cleared here.
+// pq_snappy decompresses every row with src_len > 0 in place.  pq_levels
+// decodes definition levels of width 1 for `nrows` rows -> {validity bool
+// [nrows], map int32 [nrows] (map[first_row + j]: the row of the page's j-th
+// stored value), stored int32 [pages]}.  pq_plain writes the PLAIN pages and
+// pq_rle_values the dictionary-index and RLE-boolean pages of `desc` into
+// `out`, uint8 viewed as rows of out_width bytes; rows of other pages and
+// null rows are left as they are.  map and stored come from pq_levels, or
+// are both absent for a column without nulls.  in_width is the stored width:
+// 0 for booleans (bits), 4 or 8 little-endian, or 1..8 big-endian bytes.
+// dict holds dict_n values of out_width bytes; without it the index itself
+// is stored, and must be < dict_n.  pq_dict_strings decodes the one
+// dictionary page `desc` [1, 12] of n PLAIN BYTE_ARRAY values with `total`
+// bytes -> {offsets int64 [n + 1], bytes uint8 [total]}.
+void pq_snappy(Tensor buf, Tensor desc, Tensor status);
+std::vector<Tensor> pq_levels(Tensor buf, Tensor desc, int64_t nrows,
+                              Tensor status);
+void pq_plain(Tensor buf, Tensor desc, OptTensor map, OptTensor stored,
+              Tensor out, int64_t in_width, bool big_endian,
+              int64_t out_width, Tensor status);
+void pq_rle_values(Tensor buf, Tensor desc, OptTensor map, OptTensor stored,
+                   OptTensor dict, int64_t dict_n, Tensor out,
+                   int64_t out_width, Tensor status);
+std::vector<Tensor> pq_dict_strings(Tensor buf, Tensor desc, int64_t n,
+                                    int64_t total, Tensor status);

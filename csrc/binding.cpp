@@ -86,6 +86,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one column's bytes: segment copy, or unescape where quoted");
   m.def("csv_precheck", &csv_precheck,
         "status 0 -> 2 where pyarrow's CSV converters differ");
+  m.def("pq_snappy", &pq_snappy,
+        "raw Snappy blocks of a page table, one wave per page, in place");
+  m.def("pq_levels", &pq_levels,
+        "definition levels -> (validity, row of each stored value, stored "
+        "values per page)");
+  m.def("pq_plain", &pq_plain,
+        "PLAIN fixed-width and boolean pages -> rows of a column");
+  m.def("pq_rle_values", &pq_rle_values,
+        "RLE / bit-packed hybrid pages -> dictionary gather, codes or "
+        "booleans");
+  m.def("pq_dict_strings", &pq_dict_strings,
+        "PLAIN BYTE_ARRAY dictionary page -> (offsets, bytes)");
   m.def("levenshtein", &levenshtein,
         "ASCII Levenshtein distance, one thread per row pair");
   m.def("bpe_encode", &bpe_encode,

@@ -124,12 +124,16 @@ def _hive_typed(values: List[str]):
 
 def read_parquet(path, columns: Optional[List[str]] = None,
                  io_config=None, hive_partitioning: bool = True,
+                 device_decode: Optional[bool] = None,
                  **kwargs) -> DataFrame:
+    """`device_decode`: None or True decode local files on the execution
+    device when it is a GPU (kernels/parquet.py); False, a CPU device, and
+    remote inputs are decoded by pyarrow on the host."""
     from . import readers
     paths = _expand_paths(path, io_config)
     schema = readers.infer_schema(paths[0], "parquet",
                                   storage_options=io_config)
-    read_options = None
+    read_options = {"device_decode": device_decode}
     if hive_partitioning:
         per, keys = _parse_hive_partitions(paths)
         if keys:
@@ -144,9 +148,9 @@ def read_parquet(path, columns: Optional[List[str]] = None,
                 for pth, v in zip(paths, vals):
                     hive_parts.setdefault(pth, {})[k] = v
             schema = Schema(schema.fields() + hive_fields)                 if hasattr(schema, "fields") else schema
-            read_options = {"hive_parts": hive_parts,
-                            "hive_fields": [(f.name, f.dtype)
-                                            for f in hive_fields]}
+            read_options.update(hive_parts=hive_parts,
+                                hive_fields=[(f.name, f.dtype)
+                                             for f in hive_fields])
     b = LogicalPlanBuilder.from_scan(schema, paths, "parquet",
                                      storage_options=io_config,
                                      read_options=read_options)

@@ -1,7 +1,8 @@
 """File readers: host decode (pyarrow) -> H2D to HBM.  Ref:
 /root/reference/src/daft-parquet/src/read.rs (read_parquet_bulk :342),
 daft-csv, daft-json.  Row-group streaming + column/limit pushdown here;
-GPU-side page decode is a later-round upgrade."""
+local parquet and csv files on a GPU are decoded there instead
+(kernels/parquet.py, kernels/csv.py)."""
 from __future__ import annotations
 
 import json as _json
@@ -103,11 +104,16 @@ def read_file(path: str, file_format: str, columns: Optional[List[str]],
 def read_file_inner(path, file_format, columns, predicate, limit,
                     read_options, device,
                     row_groups=None, raw=None) -> Iterator[RecordBatch]:
-    """`raw` is a csv file's content where a prefetching thread has read it
-    for the device decoder."""
+    """`raw` is what a prefetching thread has prepared for the device
+    decoder: a csv file's content, or a parquet file's staged row groups."""
     if file_format == "parquet":
-        yield from _read_parquet(path, columns, limit, device, predicate,
-                                 row_groups=row_groups)
+        from ..kernels import parquet as device_parquet
+        if device_parquet.eligible(path, read_options, device):
+            yield from device_parquet.read_file_device(
+                path, columns, limit, device, predicate, row_groups, raw)
+        else:
+            yield from _read_parquet(path, columns, limit, device, predicate,
+                                     row_groups=row_groups)
     elif file_format == "ipc":
         import pyarrow as pa
         with pa.ipc.open_file(path) as r:
@@ -203,10 +209,31 @@ def read_files_prefetch(paths: List[str], file_format: str,
         return file_format == "csv" and device_csv.eligible(
             _open_input(pth, storage_options), read_options, device)
 
+    def device_parquet_file(pth):
+        from ..kernels import parquet as device_parquet
+        return file_format == "parquet" and device_parquet.eligible(
+            _open_input(pth, storage_options), read_options, device)
+
+    def file_columns(pth):
+        # as read_file does: hive columns come from the path, not the file
+        hive = (read_options or {}).get("hive_parts") or {}
+        if columns is None or hive.get(pth) is None:
+            return columns
+        names = {n for n, _dt in read_options.get("hive_fields") or []}
+        return [c for c in columns if c not in names] or None
+
     def load(task):
         tpaths, rgs = task
         out = []
         for pth in tpaths:
+            if device_parquet_file(pth):
+                # the thread does the host stage (metadata, page headers,
+                # the chunks' bytes); the consuming thread uploads and
+                # decodes
+                from ..kernels import parquet as device_parquet
+                out.append((pth, list(device_parquet.host_stage(
+                    pth, file_columns(pth), predicate, rgs)), rgs))
+                continue
             if device_csv_file(pth):
                 # the thread only reads the bytes; the consuming thread
                 # decodes them on the device.  A file beyond one block is
@@ -240,7 +267,9 @@ def read_files_prefetch(paths: List[str], file_format: str,
                 if isinstance(rb, tuple):
                     yield from read_file(rb[0], file_format, columns,
                                          predicate, None, storage_options,
-                                         read_options, device, raw=rb[1])
+                                         read_options, device,
+                                         row_groups=rb[2] if len(rb) > 2
+                                         else None, raw=rb[1])
                 elif str(device) == "cpu":
                     yield rb
                 else:

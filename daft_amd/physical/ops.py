@@ -203,8 +203,9 @@ class InMemorySourceOp(PhysicalOp):
 
 
 class ScanOp(PhysicalOp):
-    """File scan: host decode (pyarrow) -> H2D transfer -> device batches
-    (ref: sources/scan_task.rs; GPU page decode is a later-round upgrade)."""
+    """File scan -> device batches: local parquet and csv files are decoded
+    on the GPU, everything else on the host (pyarrow) and then transferred
+    (ref: sources/scan_task.rs)."""
 
     def __init__(self, schema: Schema, paths: List[str], file_format: str,
                  storage_options: dict, read_options: dict,
