@@ -295,6 +295,47 @@ Tensor csv_extract(Tensor data, Tensor sep_pos, int64_t ncols, int64_t row0,
 void csv_precheck(Tensor offsets, Tensor bytes, Tensor status, int64_t kind,
                   int64_t scale);
 
+// JSON-lines structure of one chunk (json.hip): `data` uint8 [n], n < 2^31,
+// 16-byte aligned, beginning at a record start.  json_structure returns
+// {structmask int16 [ceil(n / 4096) * 256] (bit i of entry k: byte 16 k + i
+// is one of { } [ ] : , '\n' outside strings), depth_in, tok_base, close_base
+// int32 [ceil(n / 4096)] (nesting depth, tokens and record ends before each
+// tile), info int32 [8]}.  info: [0] error bits (1 irregular, 2 invalid UTF-8,
+// 4 a run of 64 or more '\', 8 depth below 0 or a line end inside a record,
+// 16 a key with a backslash, 32 a key outside the names, 64 a key twice in a
+// record, 128 a bad escape or lone surrogate, 256 a raw byte < 0x20 in a
+// string), [1] UTF-8 continuation bytes claimed minus present, [2] one past
+// the last '\n' at depth 0 (consumed), [3] the token count T, [4] 1 when the
+// chunk ends inside a string, [5] the longest record's bytes, [6] the records
+// before `consumed`, [7] the record ends R of the whole chunk.  json_tokens
+// returns int32 [2, T] in byte order: positions, and row << 2 | kind with
+// kind 0 a record's '{', 1 a depth-1 ':', 2 a depth-1 ',', 3 the record's
+// '}'.  json_keys packs 1..256 names of at most 2048 bytes (hash table,
+// offsets, bytes) into a host int32 tensor for the LDS of json_fields, which
+// checks the tokens before `consumed`, fills info[6] and returns {field_tok
+// int32 [ncols, R] (the ':' token of each name per row, -1 where absent),
+// row_end int32 [R]}.  json_values returns, for the first `nrows` rows,
+// {kinds uint8 [ncols, nrows] (0 null or absent, 1 false, 2 true, 3 number,
+// 4 string, 5 nested), raw_start, raw_len int64 [ncols, nrows] (the trimmed
+// value text, a string's with its quotes), ulen int64 [ncols, nrows] (a
+// string's unescaped length), seen int32 [ncols] (bit k: kind k occurs; 256:
+// a string holds a backslash)} and fills info[5].  json_extract writes one
+// column's bytes for out_offsets int64 [nrows + 1] ending in `total`:
+// without `unescape` a segment copy from raw_start, else the content of the
+// kind-4 rows with their escapes decoded.
+Tensor json_keys(std::vector<std::string> names);
+std::vector<Tensor> json_structure(Tensor data);
+Tensor json_tokens(Tensor data, Tensor structmask, Tensor depth_in,
+                   Tensor tok_base, Tensor close_base, int64_t T);
+std::vector<Tensor> json_fields(Tensor data, Tensor tokens, int64_t consumed,
+                                int64_t R, Tensor keys, int64_t ncols,
+                                Tensor info);
+std::vector<Tensor> json_values(Tensor data, Tensor tokens, Tensor field_tok,
+                                Tensor row_end, int64_t nrows, Tensor info);
+Tensor json_extract(Tensor data, Tensor kinds, Tensor raw_start,
+                    Tensor raw_len, Tensor out_offsets, int64_t total,
+                    bool unescape);
+
 // Parquet page decode (parquet.hip).  `buf` uint8, 16-byte aligned, holds a
 // row group's uploaded column-chunk bytes and the decompression arena behind
 // them; `desc` int64 [pages, 12] is the page table laid out at the top of

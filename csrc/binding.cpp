@@ -86,6 +86,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one column's bytes: segment copy, or unescape where quoted");
   m.def("csv_precheck", &csv_precheck,
         "status 0 -> 2 where pyarrow's CSV converters differ");
+  m.def("json_keys", &json_keys,
+        "schema names -> hash table, offsets and bytes for json_fields");
+  m.def("json_structure", &json_structure,
+        "JSON-lines chunk -> (structural masks, tile depth, token and record "
+        "bases, info): escape-aware quote parity, depth, UTF-8 checks");
+  m.def("json_tokens", &json_tokens,
+        "depth-1 tokens in byte order: position, kind and row");
+  m.def("json_fields", &json_fields,
+        "token grammar and keys -> (field_tok [ncols, R], row_end)");
+  m.def("json_values", &json_values,
+        "value kinds, spans and unescaped string lengths per (column, row)");
+  m.def("json_extract", &json_extract,
+        "one column's bytes: segment copy, or unescape where escaped");
   m.def("pq_snappy", &pq_snappy,
         "raw Snappy blocks of a page table, one wave per page, in place");
   m.def("pq_levels", &pq_levels,

@@ -60,6 +60,7 @@
 // that are not selected are never touched.
 #include "common.h"
 #include "block_rank.h"
+#include "bytes16.h"
 #include "host_args.h"
 #include "api.h"
 
@@ -83,46 +84,6 @@ enum {
 };
 
 // ---------------------------------------------------------------------------
-// 16 bytes of a thread
-// ---------------------------------------------------------------------------
-struct Bytes16 {
-  uint64_t lo, hi;
-};
-
-// data[base, base + 16) with zeros from n on; base is a multiple of 16 and
-// data is 16-byte aligned
-DEV_INLINE Bytes16 load16(const uint8_t* data, int64_t n, int64_t base) {
-  Bytes16 b{0, 0};
-  if (base + 16 <= n) {
-    uint4 v = *(const uint4*)(data + base);
-    b.lo = v.x | ((uint64_t)v.y << 32);
-    b.hi = v.z | ((uint64_t)v.w << 32);
-  } else {
-    for (int i = 0; i < 8 && base + i < n; ++i)
-      b.lo |= (uint64_t)data[base + i] << (8 * i);
-    for (int i = 8; i < 16 && base + i < n; ++i)
-      b.hi |= (uint64_t)data[base + i] << (8 * (i - 8));
-  }
-  return b;
-}
-
-DEV_INLINE uint32_t byte_of(const Bytes16& b, int i) {
-  return (uint32_t)((i < 8 ? b.lo >> (8 * i) : b.hi >> (8 * (i - 8))) & 0xFF);
-}
-
-DEV_INLINE uint32_t eq_mask(const Bytes16& b, uint32_t c) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) m |= (uint32_t)(byte_of(b, i) == c) << i;
-  return m;
-}
-
-DEV_INLINE int wave_sum(int v) {
-  for (int off = WAVE / 2; off; off >>= 1) v += __shfl_xor(v, off, WAVE);
-  return v;
-}
-
-// ---------------------------------------------------------------------------
 // summary: quote parity and UTF-8 evidence of a tile
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(kCsvBlock)
@@ -131,38 +92,9 @@ csv_summary_kernel(const uint8_t* data, int64_t n, int32_t* tile_parity,
   __shared__ int32_t wpar[kCsvWaves];
   const int64_t base = (int64_t)blockIdx.x * kCsvTile + threadIdx.x * 16;
   Bytes16 b{0, 0};
-  uint32_t nx = 0;  // the 3 bytes after the thread's 16
-  if (base < n) {
-    b = load16(data, n, base);
-    if ((b.hi >> 40) & 0x808080) {  // the last three bytes are not all ASCII
-      for (int j = 0; j < 3; ++j)
-        if (base + 16 + j < n) nx |= (uint32_t)data[base + 16 + j] << (8 * j);
-    }
-  }
+  if (base < n) b = load16(data, n, base);
   int diff = 0;
-  bool bad = false;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    uint32_t c = byte_of(b, i);
-    if (c < 0x80) continue;
-    if (c < 0xC0) {
-      --diff;
-      continue;
-    }
-    int k = c < 0xE0 ? 1 : c < 0xF0 ? 2 : 3;
-    uint32_t lo = c == 0xE0 ? 0xA0 : c == 0xF0 ? 0x90 : 0x80;
-    uint32_t hi = c == 0xED ? 0x9F : c == 0xF4 ? 0x8F : 0xBF;
-    if (c < 0xC2 || c > 0xF4) bad = true;
-#pragma unroll
-    for (int j = 1; j <= 3; ++j) {
-      if (j > k || base + i + j >= n) continue;  // cut off by the chunk end
-      int at = i + j;
-      uint32_t cb = at < 16 ? byte_of(b, at < 16 ? at : 0)
-                            : (nx >> (8 * (at - 16))) & 0xFF;
-      ++diff;
-      if (cb < (j == 1 ? lo : 0x80u) || cb > (j == 1 ? hi : 0xBFu)) bad = true;
-    }
-  }
+  bool bad = utf8_evidence(data, n, base, b, &diff);
   if (bad) atomicOr(info + kInfoErr, kBadUtf8);
   int32_t total = block_sum(diff);
   if (threadIdx.x == 0 && total) atomicAdd(info + kInfoCont, total);

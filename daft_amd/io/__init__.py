@@ -226,13 +226,23 @@ def read_csv(path, has_headers: bool = True, delimiter: str = ",",
         read_options=read_options))
 
 
-def read_json(path, io_config=None, **kwargs) -> DataFrame:
+def read_json(path, io_config=None, device_decode: Optional[bool] = None,
+              **kwargs) -> DataFrame:
+    """`device_decode=True` decodes local, uncompressed JSON-lines files on
+    the execution device when it is a GPU (kernels/jsonl.py).  None (the
+    default, as the device path measured no faster end to end), False, a CPU
+    device, and compressed or remote inputs are decoded by pyarrow on the
+    host."""
     from . import readers
     paths = _expand_paths(path)
     sch = readers.infer_schema(paths[0], "json",
                                storage_options=io_config)
+    # the device decoder finds and types its columns by the scan schema
+    read_options = {"device_decode": device_decode,
+                    "schema": {f.name: f.dtype for f in sch}}
     return DataFrame(LogicalPlanBuilder.from_scan(
-        sch, paths, "json", storage_options=io_config))
+        sch, paths, "json", storage_options=io_config,
+        read_options=read_options))
 
 
 def read_text(path, line_column: str = "text") -> DataFrame:
@@ -245,9 +255,9 @@ def read_text(path, line_column: str = "text") -> DataFrame:
     return from_pydict({line_column: lines})
 
 
-def read_jsonl(path) -> DataFrame:
+def read_jsonl(path, device_decode: Optional[bool] = None) -> DataFrame:
     """Read newline-delimited JSON (alias of read_json for local files)."""
-    return read_json(path)
+    return read_json(path, device_decode=device_decode)
 
 
 def read_sql(sql: str, conn_factory, partition_col=None, **kwargs) -> DataFrame:

@@ -1,8 +1,8 @@
 """File readers: host decode (pyarrow) -> H2D to HBM.  Ref:
 /root/reference/src/daft-parquet/src/read.rs (read_parquet_bulk :342),
 daft-csv, daft-json.  Row-group streaming + column/limit pushdown here;
-local parquet and csv files on a GPU are decoded there instead
-(kernels/parquet.py, kernels/csv.py)."""
+local parquet, csv and json-lines files on a GPU are decoded there instead
+(kernels/parquet.py, kernels/csv.py, kernels/jsonl.py)."""
 from __future__ import annotations
 
 import json as _json
@@ -130,7 +130,12 @@ def read_file_inner(path, file_format, columns, predicate, limit,
         else:
             yield from _read_csv(path, columns, read_options, device)
     elif file_format == "json":
-        yield from _read_json(path, columns, device)
+        from ..kernels import jsonl as device_json
+        if device_json.eligible(path, read_options, device):
+            yield from device_json.read_file_device(path, columns,
+                                                    read_options, device, raw)
+        else:
+            yield from _read_json(path, columns, device)
     elif file_format == "warc":
         yield from _read_warc(path, columns, device)
     else:
@@ -204,10 +209,14 @@ def read_files_prefetch(paths: List[str], file_format: str,
 
     tasks = plan_scan_tasks(paths, file_format, storage_options)
 
-    def device_csv_file(pth):
-        from ..kernels import csv as device_csv
-        return file_format == "csv" and device_csv.eligible(
-            _open_input(pth, storage_options), read_options, device)
+    def device_text_decoder(pth):
+        # csv or json lines: the device decoder of either takes raw bytes
+        if file_format not in ("csv", "json"):
+            return None
+        from ..kernels import csv as device_csv, jsonl as device_json
+        mod = device_csv if file_format == "csv" else device_json
+        return mod if mod.eligible(_open_input(pth, storage_options),
+                                   read_options, device) else None
 
     def device_parquet_file(pth):
         from ..kernels import parquet as device_parquet
@@ -234,13 +243,13 @@ def read_files_prefetch(paths: List[str], file_format: str,
                 out.append((pth, list(device_parquet.host_stage(
                     pth, file_columns(pth), predicate, rgs)), rgs))
                 continue
-            if device_csv_file(pth):
+            device_text = device_text_decoder(pth)
+            if device_text is not None:
                 # the thread only reads the bytes; the consuming thread
                 # decodes them on the device.  A file beyond one block is
                 # not held whole: the consumer streams it in blocks.
-                from ..kernels import csv as device_csv
                 raw = None
-                if os.path.getsize(pth) <= device_csv.BLOCK_BYTES:
+                if os.path.getsize(pth) <= device_text.BLOCK_BYTES:
                     with open(pth, "rb") as f:
                         raw = f.read()
                 out.append((pth, raw))

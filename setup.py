@@ -29,6 +29,7 @@ setup(
                 "csrc/strtransform.hip",
                 "csrc/strparse.hip",
                 "csrc/csv.hip",
+                "csrc/json.hip",
                 "csrc/parquet.hip",
                 "csrc/regex.hip",
                 "csrc/multimodal.hip",
